@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: CLT Gaussian noise (AWGN) sample generation on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
   N > 1: either under a launcher (python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...,
   RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment) or plainly as above -- then this process
   starts the N ranks itself as child processes before touching any GPU (launch_ranks) and passes rank 0's
@@ -51,6 +51,26 @@ NSAMP = 1_000_000_000
 WARM_STATE = 16                  # 2*log2(256): the reference test's warm-up (rng.py:161-162)
 HBM_PEAK_GBS = 8000.0            # /opt/skills/guides/MI355X_MICROARCH.md: 8 TB/s spec
 VALU_OPS_PER_SAMPLE = None       # filled from the generated network's op count
+DUMP_HEAD = 1 << 20              # --dump-outputs: the first samples of the last timed step's output, contiguous,
+DUMP_SAMPLE = 1 << 23            # and this many more at fixed, seeded positions across all of it (36 MB of float32 in all)
+DUMP_SEED = 2026
+
+
+def dump_positions():
+    """The sorted positions in the step's NSAMP samples that awgn_sample.npy holds: the same on every run."""
+    import numpy as np
+    return np.sort(np.random.default_rng(DUMP_SEED).integers(0, NSAMP, DUMP_SAMPLE))
+
+
+def dump_outputs(d, buf):
+    """What the timed path handed its caller in the last timed step (`buf`, NSAMP int8 samples), as float32 .npy under d:
+    awgn_head.npy (its first DUMP_HEAD samples) and awgn_sample.npy (the samples at dump_positions())."""
+    import numpy as np
+    import torch
+    os.makedirs(d, exist_ok=True)
+    idx = torch.from_numpy(dump_positions()).to(buf.device)
+    np.save(os.path.join(d, "awgn_head.npy"), buf[:DUMP_HEAD].float().cpu().numpy())
+    np.save(os.path.join(d, "awgn_sample.npy"), buf[idx].float().cpu().numpy())
 
 
 def stream_clock_record():
@@ -259,7 +279,11 @@ def main():
     ap.add_argument("--no-extra", action="store_true")
     ap.add_argument("--launch-check", action="store_true",
                     help="rendezvous only (gloo, no GPU): every rank joins, one all-reduce, rank 0 prints a JSON line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write rank 0's output of the last one to DIR/*.npy (float32; see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # started as plain `python bench.py --gpus N`: this process becomes the launcher and never touches
@@ -400,6 +424,8 @@ def main():
         verified = verified and bool(np.array_equal(tail_d.cpu().numpy(),
                                                     m.awgn(u.state_at(WARM_STATE + NSAMP - 4096), 0, 4096, fast=True)))
     del head_d, tail_d
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, buf)            # before the extras below reuse buf
 
     value = world * args.steps * NSAMP / dt / 1e9
     kern_avg_ms = kern_ms / max(calls, 1)                 # per LAUNCH of the sample kernel

@@ -101,3 +101,33 @@ def test_single_gpu_line_has_the_contract_fields():
     assert 0 < rf["valu_frac"] < rf["valu_frac_issued"] < rf["valu_frac_issued_of_measured_attainable"] < rf["valu_frac_issued_of_1wave_ceiling"] < 1
     assert rf["kernel_ms_avg"] / rf["steps_per_launch"] <= out["ms_per_step"] * 1.05
     assert out["config"]["clock_ramp_steps"] >= 0 and out["extra"]["cold_start"]["ms_per_step"] > 0
+
+
+def test_steps_below_one_are_refused():
+    r = _run(["--steps", "0"], timeout=120)
+    assert r.returncode == 2 and "--steps" in r.stderr and not r.stdout.strip()
+
+
+@pytest.mark.gpu
+def test_dump_outputs_hold_the_last_timed_step(gpu, oracle, tmp_path):
+    """--dump-outputs DIR: float32 .npy of what the last timed step delivered, at most 64 MB in all, equal to the oracle's
+    stream there.  With no ramp steps that step is the run's sixth: step 0 (the parity copy), 2 cold, 1 warm-up, 2 timed."""
+    import numpy as np
+    import bench
+    r = _run(["--steps", "2", "--warmup", "1", "--no-extra", "--no-cpu-baseline", "--dump-outputs", str(tmp_path)],
+             env={"BENCH_RAMP_STEPS": "0"}, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = json.loads(r.stdout)
+    assert out["steps"] == 2 and out["ms_per_step"] > 0 and out["config"]["verified_vs_oracle"] is True
+    files = sorted(tmp_path.glob("*.npy"))
+    assert [f.name for f in files] == ["awgn_head.npy", "awgn_sample.npy"]
+    assert sum(f.stat().st_size for f in files) <= 64 << 20
+    head, sample = np.load(tmp_path / "awgn_head.npy"), np.load(tmp_path / "awgn_sample.npy")
+    assert head.dtype == sample.dtype == np.float32 and head.shape == (bench.DUMP_HEAD,) and sample.shape == (bench.DUMP_SAMPLE,)
+    u = gpu.LUTOPT.shipped(256, device=0)
+    m = oracle.Lutopt(path=oracle.data_path(256))
+    first = bench.WARM_STATE + 5 * bench.NSAMP
+    assert np.array_equal(head, m.awgn(u.state_at(first), 0, bench.DUMP_HEAD, fast=True).astype(np.float32))
+    pos = bench.dump_positions()
+    for i in np.linspace(0, bench.DUMP_SAMPLE - 1, 64).astype(np.int64):
+        assert sample[i] == m.awgn(u.state_at(first + int(pos[i])), 0, 1, fast=True)[0], int(pos[i])
