@@ -50,12 +50,86 @@ int use_device(int device) {
     return BBB_OK;
 }
 
+namespace {
+
+// A device buffer of T (Pinned: page-locked host memory) that grows to exactly the size asked for: the old buffer is freed
+// first, nothing is allocated ahead.  hipFree waits for the device, so a grow is a host synchronisation.  Move-only; the
+// destructor frees it.
+template <typename T, bool Pinned = false>
+struct DevBuf {
+    T *p = nullptr;
+    size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    DevBuf &operator=(DevBuf &&o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); return *this; }   // (o frees the old one)
+    ~DevBuf() { if (p) (void)(Pinned ? hipHostFree(p) : hipFree(p)); }
+    operator T *() const { return p; }
+    int grow(size_t need) {
+        if (cap >= need) return BBB_OK;
+        if (p) BBB_HIP(Pinned ? hipHostFree(p) : hipFree(p));
+        p = nullptr;
+        cap = 0;
+        BBB_HIP(Pinned ? hipHostMalloc((void **)&p, need * sizeof(T), hipHostMallocDefault) : hipMalloc((void **)&p, need * sizeof(T)));
+        cap = need;
+        return BBB_OK;
+    }
+};
+
+// A hipEventDisableTiming event, created by its first record (a host-only handle creates none); the destructor destroys it.
+struct Event {
+    hipEvent_t e = nullptr;
+    Event() = default;
+    Event(Event &&o) noexcept : e(o.e) { o.e = nullptr; }
+    Event &operator=(Event &&o) noexcept { std::swap(e, o.e); return *this; }
+    ~Event() { if (e) (void)hipEventDestroy(e); }
+    operator hipEvent_t() const { return e; }
+    int record(hipStream_t s) {
+        if (!e) BBB_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        BBB_HIP(hipEventRecord(e, s));
+        return BBB_OK;
+    }
+};
+
+// Device buffers and the event behind the last kernel that read them (read_pending: one has since the last grow).  A writer
+// on another stream waits for that reader; growing frees the old buffers, so the host first synchronises with it.
+template <size_t N>
+struct ReadGuarded {
+    DevBuf<uint32_t> buf[N];
+    Event last_read;
+    bool read_pending = false;
+    bool fits(const size_t (&need)[N]) const {
+        for (size_t i = 0; i < N; i++)
+            if (buf[i].cap < need[i]) return false;
+        return true;
+    }
+    int grow(const size_t (&need)[N]) {
+        if (fits(need)) return BBB_OK;
+        if (read_pending) BBB_HIP(hipEventSynchronize(last_read));
+        read_pending = false;
+        for (size_t i = 0; i < N; i++)
+            if (const int rc = buf[i].grow(need[i])) return rc;
+        return BBB_OK;
+    }
+    int wait_read(hipStream_t s) const {
+        if (read_pending) BBB_HIP(hipStreamWaitEvent(s, last_read, 0));
+        return BBB_OK;
+    }
+    int mark_read(hipStream_t s) {
+        if (const int rc = last_read.record(s)) return rc;
+        read_pending = true;
+        return BBB_OK;
+    }
+};
+enum { kStates = 0, kPlanes = 1 };     // the two buffers of a set of generator start states
+
+}  // namespace
+
 // device copy of the doubling matrices for one segment length L
 struct JumpPlan {
     GF2Mat B;                     // the per-generator jump itself (host copy, for the first 16 states)
     GF2Mat Bt;                    // its transpose: y = B x as the XOR of the rows of Bt that x selects (GF2Mat::matvec_t)
-    uint32_t *d_cols = nullptr;   // [levels][15][k/4 * 16 * W32] nibble tables of M^(j*16^e)
-    uint32_t *d_top = nullptr;    // [kSeedTopTables][k/4 * 16 * W32] tables of M^(d * 16^4), d = 1 .. 31: digits 4 and 5 as ONE level
+    DevBuf<uint32_t> d_cols;      // [levels][15][k/4 * 16 * W32] nibble tables of M^(j*16^e)
+    DevBuf<uint32_t> d_top;       // [kSeedTopTables][k/4 * 16 * W32] tables of M^(d * 16^4), d = 1 .. 31: digits 4 and 5 as ONE level
                                   // (awgn_seed_states_launch; built on first use: ensure_top_tables)
     uint32_t qcol64[32] = {0};    // PRBS plans (n <= 31): column c of B^64 -- the step between two generators of one consumer lane
     int levels = 0;
@@ -79,49 +153,44 @@ struct bbb_lutopt {
     std::unique_ptr<GF2Powers> pw;                 // powers of A
     std::map<uint64_t, JumpPlan> plans;            // keyed by L
     std::map<uint64_t, JumpPlan> prbs_plans;       // keyed by (k << 48 | L)
-    // workspace
-    uint32_t *d_states = nullptr; size_t states_cap = 0;      // [W32][G] word-major
-    uint32_t *d_planes = nullptr; size_t planes_cap = 0;      // [2][k][nlanes] (second half: generic kernel)
-    // PRBS start states of a BER trial, two pairs taken in turn (ber_run): [G] and [32][nlanes]; pp_read[b]: behind the trial
-    // kernel that last read pair b
-    uint32_t *d_pstates[2] = {nullptr, nullptr}; size_t pstates_cap[2] = {0, 0};
-    uint32_t *d_pplanes[2] = {nullptr, nullptr}; size_t pplanes_cap[2] = {0, 0};
-    hipEvent_t pp_read[2] = {nullptr, nullptr};
-    bool pp_pending[2] = {false, false};
+    // workspace.  The start states the next fill reads: [kStates] [W32][G] word-major, [kPlanes] [2][k][nlanes] (second half:
+    // generic kernel); last_read: behind the last kernel that read them (it travels with them through the prefetch swap)
+    ReadGuarded<2> cur;
+    // PRBS start states of a BER trial, two pairs taken in turn (ber_run): the planes [32][nlanes]
+    ReadGuarded<1> pp[2];
     int pp_idx = 0;
-    uint16_t *d_taps = nullptr;
-    uint32_t *d_row_off = nullptr;
-    unsigned long long *d_counters = nullptr; size_t counters_cap = 0;
-    uint32_t *d_txnoise = nullptr; size_t txnoise_cap = 0;    // TX: int8 noise samples (as words)
-    uint32_t *d_txbits = nullptr; size_t txbits_cap = 0;      // TX: packed data bits (as words)
+    DevBuf<uint16_t> d_taps;
+    DevBuf<uint32_t> d_row_off;
+    DevBuf<unsigned long long> d_counters;
+    DevBuf<uint32_t> d_txnoise;     // TX: int8 noise samples (as words)
+    DevBuf<uint32_t> d_txbits;      // TX: packed data bits (as words)
     // fused TX (bbb_tx_fill_i16 with noise): the data bits of call s+1 are generated on the side stream while the sample
     // kernel of call s still reads its own -- two buffers, each with the event of its last reader
-    uint32_t *d_fbits[2] = {nullptr, nullptr}; size_t fbits_cap[2] = {0, 0};
-    hipEvent_t fbits_read[2] = {nullptr, nullptr}, fbits_ready = nullptr;
+    ReadGuarded<1> fbits[2];
+    Event fbits_ready;
     // staged TX: the data bits of a noise kernel's windows, written on the staging slot's arithmetic stream in front of the sample kernel, read by the
     // slot's movers.  TWO buffers per slot, taken in turn (round 5): the bits of the slot's next kernel then do not wait for the movers of its last
     // one -- only the sample kernel does, for the staging slot itself -- and 55 us leave the gap between two noise kernels.  The readers
     // of the buffer taken now are the movers of the slot's kernel BEFORE last, which the last kernel -- queued on this same stream -- waited for.
-    uint32_t *d_mbits[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}}; size_t mbits_cap[2][2] = {{0, 0}, {0, 0}};
+    // (Their last reader is the slot's: a grow synchronises with stage_free.)
+    DevBuf<uint32_t> d_mbits[2][2];
     unsigned mbits_turn[2] = {0, 0};
-    hipEvent_t ber_join = nullptr;       // ber_run: behind the PRBS seeding on the side stream
     // BER trials (round 5): the generators' start states from awgn_seed_head_launch / _tail_planes_launch (two launches: the first 65536 states packed,
     // u32[8][65536], then the planes [256][nlanes] directly), two buffer pairs taken in turn like the PRBS pairs; bs_read[b]: behind the
     // trial kernel that last read pair b; bs_ready[b]: behind the seeding that filled it (on the caller's stream or an arithmetic one)
-    uint32_t *d_bstates[2] = {nullptr, nullptr}; size_t bstates_cap[2] = {0, 0};
-    uint32_t *d_bplanes[2] = {nullptr, nullptr}; size_t bplanes_cap[2] = {0, 0};
-    hipEvent_t bs_read[2] = {nullptr, nullptr}, bs_ready[2] = {nullptr, nullptr};
+    // (kept as parallel arrays: tests/test_sched_model.py's mutant "ber_buffer_reuse" takes the pair's read wait out by its text)
+    DevBuf<uint32_t> d_bstates[2], d_bplanes[2];
+    Event bs_read[2], bs_ready[2];
     bool bs_pending[2] = {false, false}, bs_valid[2] = {false, false};
     uint64_t bs_first[2] = {0, 0}, bs_L[2] = {0, 0}, bs_G[2] = {0, 0};
     int bs_idx = 0;
-    unsigned long long *h_counters = nullptr; size_t h_counters_cap = 0;     // pinned: the read-back of bbb_ber_trials / bbb_ber_sweep_multi
+    DevBuf<unsigned long long, true> h_counters;     // pinned: the read-back of bbb_ber_trials / bbb_ber_sweep_multi
     // d_counters is zeroed BEHIND the read-back of the call that used it (counters_zeroed: the event behind that memset), so that the
     // next call's seeding is the first thing it queues; a call on another stream waits for the event
-    hipEvent_t counters_zeroed = nullptr;
+    Event counters_zeroed;
     bool counters_clean = false;
-    bool fbits_pending[2] = {false, false};
     int fbits_slot = 0;
-    // which stream position the planes in d_planes currently describe
+    // which stream position the planes in cur currently describe
     bool planes_valid = false;
     uint64_t planes_first = 0, planes_L = 0, planes_G = 0;
     unsigned max_waves = 1024;
@@ -131,11 +200,12 @@ struct bbb_lutopt {
         bool valid = false;
         uint64_t first = 0, L = 0, G = 0;
         unsigned nlanes = 0;
-        uint32_t *d_states = nullptr; size_t states_cap = 0;
-        uint32_t *d_planes = nullptr; size_t planes_cap = 0;
-        hipEvent_t seeded = nullptr;      // recorded on the side stream after seeding
-        hipEvent_t last_read = nullptr;   // recorded on the main stream after the last kernel that read these buffers
-        bool read_pending = false;
+        ReadGuarded<2> set;               // the second set of start-state buffers (as cur)
+        // recorded on the side stream after seeding; created by the first seeding (seed_announced, whose wait for it
+        // tests/test_sched_model.py's mutant "untaken_hint" takes out by its text)
+        hipEvent_t seeded = nullptr;
+        ~Prefetch() { if (seeded) (void)hipEventDestroy(seeded); }
+        bool matches(uint64_t f, uint64_t l, uint64_t g) const { return valid && first == f && L == l && G == g; }
     } pf;
     hipStream_t side = nullptr;
     // The stream the library's plane-touching work of the current call goes to: the caller's stream, or -- for the
@@ -143,7 +213,7 @@ struct bbb_lutopt {
     // not queue behind the caller-visible completion of this one (see staged_fill).
     hipStream_t cs = nullptr;
     bool cs_valid = false;
-    hipEvent_t handover = nullptr;
+    Event handover;
     bool staged_mode = false;             // bbb_lutopt_set_staged
     bool has_stream = false;              // a bbb_awgn_stream is open on this handle
     // internal streams: arithmetic (one per staging slot: consecutive sample kernels go to alternate streams, so that the
@@ -151,15 +221,15 @@ struct bbb_lutopt {
     // processed while kernel s still runs instead of between the two: 21-27 us per step in profiles/r03_ramp_clock_per_launch.log)
     // and the piece mover
     hipStream_t xs2[2] = {nullptr, nullptr}, ys = nullptr;
-    uint32_t *d_stage[2] = {nullptr, nullptr}; size_t stage_cap[2] = {0, 0};
-    hipEvent_t stage_free[2] = {nullptr, nullptr};     // recorded behind the mover that read the buffer (behind ALL its movers: queue_mover_with)
+    DevBuf<uint32_t> d_stage[2];
+    Event stage_free[2];                  // recorded behind the mover that read the buffer (behind ALL its movers: queue_mover_with)
     bool stage_busy[2] = {false, false};
     int stage_slot = 0;
-    hipEvent_t ev_user = nullptr;
+    Event ev_user;
     int pf_waited_slot = -1;              // staging slot whose mover the pending prefetch's seeding waited for
     uint64_t stage_gen[2] = {0, 0};       // movers queued on the slot so far
     uint64_t pf_waited_gen = 0;           // stage_gen[pf_waited_slot] when that seeding was queued: a later mover voids the skip
-    hipEvent_t stage_arith[2] = {nullptr, nullptr};   // recorded behind the sample kernel that filled the slot
+    Event stage_arith[2];                 // recorded behind the sample kernel that filled the slot
     // look-ahead (bbb_lutopt_set_staged(h, m), m >= 2): the sample kernel of a fill also produced the next m - 1 fills'
     // samples, which wait in its staging slot: `left` more fills of n samples, the next one at stream position `first`
     // (kind 0: bbb_awgn_fill_i8, a generator step; kind 1: bbb_tx_fill_i16 with configuration `cfg`, a TX sample index)
@@ -173,8 +243,6 @@ struct bbb_lutopt {
     bool last_fill_tx = false;            // the last sample-kernel launch was the transmitter variant (more LDS: see bbb_awgn_prefetch)
     bool last_staged_small = false;       // the last staged sample kernel was the small-footprint placement (two guest waves fit beside it)
     int staged_level = 0;                 // 0 off, 1 staged, m >= 2 staged with m fills per sample kernel
-    hipEvent_t cur_last_read = nullptr;   // same, for the buffers currently in d_states / d_planes
-    bool cur_read_pending = false;
     // optional per-call device timing of the generator kernels (bbb_lutopt_profile)
     bool profiling = false;
     struct ProfEv { hipEvent_t e0, e1, e2; };
@@ -202,13 +270,12 @@ int pad_w32(int k) {
     return 16;
 }
 
-int grow(uint32_t **p, size_t *cap, size_t need_words) {
-    if (*cap >= need_words) return BBB_OK;
-    if (*p) BBB_HIP(hipFree(*p));
-    *p = nullptr;
-    *cap = 0;
-    BBB_HIP(hipMalloc((void **)p, need_words * sizeof(uint32_t)));
-    *cap = need_words;
+// a host table to the device: *out is set only once the copy has succeeded (on failure the new buffer is freed)
+int upload(const std::vector<uint32_t> &host, DevBuf<uint32_t> *out) {
+    DevBuf<uint32_t> d;
+    if (const int rc = d.grow(host.size())) return rc;
+    BBB_HIP(hipMemcpy(d.p, host.data(), host.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    *out = std::move(d);
     return BBB_OK;
 }
 
@@ -257,8 +324,7 @@ int build_plan(const GF2Mat &M, int levels, JumpPlan *plan) {
             nibble_table(mj, &host[((size_t)e * 15 + (j - 1)) * nt]);
         }
     }
-    BBB_HIP(hipMalloc((void **)&plan->d_cols, host.size() * sizeof(uint32_t)));
-    BBB_HIP(hipMemcpy(plan->d_cols, host.data(), host.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (const int rc = upload(host, &plan->d_cols)) return rc;
     plan->levels = levels;
     plan->B = M;
     plan->Bt = M.transpose();
@@ -277,6 +343,13 @@ void first16(const JumpPlan &plan, const uint64_t *s0, uint32_t *out) {
     }
 }
 
+// the same for the handle's generators from stream position `step`: B^i A^step init
+void first16_at(const bbb_lutopt *h, const JumpPlan &plan, uint64_t step, uint32_t *out) {
+    uint64_t s0[8] = {0};
+    h->pw->apply(step, h->init, s0);
+    first16(plan, s0, out);
+}
+
 constexpr int kPlanLevels = 7;    // radix 16: up to 16^7 = 2^28 generators
 
 // the merged top level of a plan (round 5): tables of B^(d 65536), d = 1 .. 31
@@ -293,9 +366,7 @@ int ensure_top_tables(JumpPlan *plan) {
         if (d > 1) md = md.mul(m4);
         nibble_table(md, &host[(size_t)(d - 1) * nt]);
     }
-    BBB_HIP(hipMalloc((void **)&plan->d_top, host.size() * sizeof(uint32_t)));
-    BBB_HIP(hipMemcpy(plan->d_top, host.data(), host.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    return BBB_OK;
+    return upload(host, &plan->d_top);
 }
 
 int get_plan(bbb_lutopt *h, uint64_t L, JumpPlan **out) {
@@ -304,7 +375,7 @@ int get_plan(bbb_lutopt *h, uint64_t L, JumpPlan **out) {
         JumpPlan p;
         int rc = build_plan(h->pw->power(L), kPlanLevels, &p);
         if (rc) return rc;
-        it = h->plans.emplace(L, p).first;
+        it = h->plans.emplace(L, std::move(p)).first;
     }
     *out = &it->second;
     return BBB_OK;
@@ -324,7 +395,7 @@ int get_prbs_plan(bbb_lutopt *h, int k, uint64_t L, JumpPlan **out) {
             const GF2Mat qt = q.transpose();
             for (int c = 0; c < k && c < 32; c++) p.qcol64[c] = (uint32_t)qt.row(c)[0];
         }
-        it = h->prbs_plans.emplace(key, p).first;
+        it = h->prbs_plans.emplace(key, std::move(p)).first;
     }
     *out = &it->second;
     return BBB_OK;
@@ -394,8 +465,8 @@ int begin_op(bbb_lutopt *h, bool internal, bool independent_of_previous_internal
         // it to the work on the other arithmetic stream, so it does not wait for it
         const bool from_internal = h->cs == h->xs2[0] || h->cs == h->xs2[1];
         if (!(independent_of_previous_internal && internal && from_internal)) {
-            if (!h->handover) BBB_HIP(hipEventCreateWithFlags(&h->handover, hipEventDisableTiming));
-            BBB_HIP(hipEventRecord(h->handover, h->cs));
+            const int rc = h->handover.record(h->cs);
+            if (rc) return rc;
             BBB_HIP(hipStreamWaitEvent(want, h->handover, 0));
         }
     }
@@ -404,17 +475,13 @@ int begin_op(bbb_lutopt *h, bool internal, bool independent_of_previous_internal
     return BBB_OK;
 }
 
-// Every kernel that touches d_states / d_planes on the main stream is followed by this: after a prefetch swap
+// Every kernel that touches the start states (cur) on the main stream is followed by this: after a prefetch swap
 // these buffers become the side stream's, which must not seed into them while such a kernel is still running.
-int mark_planes_read(bbb_lutopt *h) {
-    if (!h->cur_last_read) BBB_HIP(hipEventCreateWithFlags(&h->cur_last_read, hipEventDisableTiming));
-    BBB_HIP(hipEventRecord(h->cur_last_read, h->cs));
-    h->cur_read_pending = true;
-    return BBB_OK;
-}
+int mark_planes_read(bbb_lutopt *h) { return h->cur.mark_read(h->cs); }
 
-// make d_planes hold the bit-sliced states A^(first + g*L) init, g < G
-int prepare_planes(bbb_lutopt *h, uint64_t first, uint64_t L, uint64_t G, unsigned nlanes) {
+// make cur hold the bit-sliced states A^(first + g*L) init, g < G.  slice_mode 1: the packed n512 kernel's layout, which is not
+// the one cached here (its caller has dropped planes_valid, and its fill kernel marks the read)
+int prepare_planes(bbb_lutopt *h, uint64_t first, uint64_t L, uint64_t G, unsigned nlanes, int slice_mode = 0) {
     if (h->planes_valid && h->planes_first == first && h->planes_L == L && h->planes_G == G) return BBB_OK;
     JumpPlan *plan;
     int rc = get_plan(h, L, &plan);
@@ -427,21 +494,18 @@ int prepare_planes(bbb_lutopt *h, uint64_t first, uint64_t L, uint64_t G, unsign
     const bool two_launch = h->k == 256 && (h->specialised || h->custom_fill) && !h->fast512 && G <= ((uint64_t)kSeedTopTables + 1) * 65536 &&
                             !env_knob("BBB_EXP_SEED_CHAIN", 0);
     const size_t states_words = two_launch && (size_t)G * h->W32 < (size_t)65536 * 8 ? (size_t)65536 * 8 : (size_t)G * h->W32;
-    if ((rc = grow(&h->d_states, &h->states_cap, states_words))) return rc;
-    if ((rc = grow(&h->d_planes, &h->planes_cap, (size_t)2 * h->k * nlanes))) return rc;
-    uint64_t s0[8];
-    h->pw->apply(first, h->init, s0);
+    if ((rc = h->cur.grow({states_words, (size_t)2 * h->k * nlanes}))) return rc;
     uint32_t s16[256];
-    first16(*plan, s0, s16);
+    first16_at(h, *plan, first, s16);
     h->planes_valid = false;
     if (two_launch) {
         if ((rc = ensure_top_tables(plan))) return rc;
-        if ((rc = awgn_seed_head_launch(h->k, plan->d_cols, s16, G, h->d_states, h->cs))) return rc;
-        rc = awgn_seed_tail_planes_launch(h->k, plan->d_top, G, h->d_states, nlanes, h->d_planes, h->cs);
+        if ((rc = awgn_seed_head_launch(h->k, plan->d_cols, s16, G, h->cur.buf[kStates], h->cs))) return rc;
+        rc = awgn_seed_tail_planes_launch(h->k, plan->d_top, G, h->cur.buf[kStates], nlanes, h->cur.buf[kPlanes], h->cs);
     } else {
-        rc = awgn_seed_launch(h->k, plan->d_cols, s16, G, h->d_states, G, nlanes, h->d_planes, h->cs);
+        rc = awgn_seed_launch(h->k, plan->d_cols, s16, G, h->cur.buf[kStates], G, nlanes, h->cur.buf[kPlanes], h->cs, slice_mode);
     }
-    if (rc) return rc;
+    if (rc || slice_mode) return rc;
     if ((rc = mark_planes_read(h))) return rc;
     h->planes_valid = true;
     h->planes_first = first; h->planes_L = L; h->planes_G = G;
@@ -450,21 +514,19 @@ int prepare_planes(bbb_lutopt *h, uint64_t first, uint64_t L, uint64_t G, unsign
 
 // the start states of (first_step, L, G): those an announced prefetch seeded on the side stream, or seeded now
 int acquire_planes(bbb_lutopt *h, uint64_t first_step, uint64_t L, uint64_t G, unsigned nlanes, bool may_use_prefetch,
-                   bool *from_prefetch = nullptr) {
+                   bool *from_prefetch = nullptr, int slice_mode = 0) {
     if (from_prefetch) *from_prefetch = false;
-    if (may_use_prefetch && h->pf.valid && h->pf.first == first_step && h->pf.L == L && h->pf.G == G) {
+    if (may_use_prefetch && h->pf.matches(first_step, L, G)) {
         if (from_prefetch) *from_prefetch = true;
         // the announced fill: its start states were seeded on the side stream -- swap them in
         BBB_HIP(hipStreamWaitEvent(h->cs, h->pf.seeded, 0));
-        std::swap(h->d_states, h->pf.d_states); std::swap(h->states_cap, h->pf.states_cap);
-        std::swap(h->d_planes, h->pf.d_planes); std::swap(h->planes_cap, h->pf.planes_cap);
-        std::swap(h->cur_last_read, h->pf.last_read); std::swap(h->cur_read_pending, h->pf.read_pending);
+        std::swap(h->cur, h->pf.set);
         h->pf.valid = false;
-        h->planes_valid = true;
+        h->planes_valid = slice_mode == 0;
         h->planes_first = first_step; h->planes_L = L; h->planes_G = G;
         return BBB_OK;
     }
-    return prepare_planes(h, first_step, L, G, nlanes);
+    return prepare_planes(h, first_step, L, G, nlanes, slice_mode);
 }
 
 // The two-kernel ("staged") form of a fill (bbb_lutopt_set_staged), PLANES form since round 3:
@@ -489,16 +551,15 @@ int acquire_planes(bbb_lutopt *h, uint64_t first_step, uint64_t L, uint64_t G, u
 // stream)` queues the kernel
 template <typename LaunchMover>
 int queue_mover_with(bbb_lutopt *h, int slot, LaunchMover launch_mover) {
-    if (!h->stage_free[slot]) BBB_HIP(hipEventCreateWithFlags(&h->stage_free[slot], hipEventDisableTiming));
     hipStream_t ms = h->stream;
+    int rc;
     // (-DBBB_EXPERIMENTS, BBB_EXP_MOVER_OWN_STREAM=1: rounds 2-4's mover on a fourth internal stream tied to the caller's by an
     // event each way, for the A/B of experiments/mover_stream_ab.py)
     const bool own_stream = env_knob("BBB_EXP_MOVER_OWN_STREAM", 0) != 0;
     if (own_stream) {
         if (!h->ys) BBB_HIP(hipStreamCreateWithFlags(&h->ys, hipStreamNonBlocking));
-        if (!h->ev_user) BBB_HIP(hipEventCreateWithFlags(&h->ev_user, hipEventDisableTiming));
         ms = h->ys;
-        BBB_HIP(hipEventRecord(h->ev_user, h->stream));
+        if ((rc = h->ev_user.record(h->stream))) return rc;
         BBB_HIP(hipStreamWaitEvent(ms, h->ev_user, 0));
     }
     BBB_HIP(hipStreamWaitEvent(ms, h->stage_arith[slot], 0));
@@ -512,17 +573,25 @@ int queue_mover_with(bbb_lutopt *h, int slot, LaunchMover launch_mover) {
         BBB_HIP(hipEventCreate(&m0)); BBB_HIP(hipEventCreate(&m1));
         BBB_HIP(hipEventRecord(m0, ms));
     }
-    int rc = launch_mover((const void *)h->d_stage[slot], ms);
-    if (rc) return rc;
+    if ((rc = launch_mover((const void *)h->d_stage[slot].p, ms))) return rc;
     if (h->profiling) {
         BBB_HIP(hipEventRecord(m1, ms));
         h->prof_mover_pending.emplace_back(m0, m1);
     }
-    BBB_HIP(hipEventRecord(h->stage_free[slot], ms));
+    if ((rc = h->stage_free[slot].record(ms))) return rc;
     h->stage_busy[slot] = true;
     h->stage_gen[slot]++;
     if (own_stream) BBB_HIP(hipStreamWaitEvent(h->stream, h->stage_free[slot], 0));
     return BBB_OK;
+}
+
+// look-ahead: the first of the fills waiting in a staging slot is taken -- its description is returned, the next one's is left
+bbb_lutopt::Ahead take_ahead(bbb_lutopt *h) {
+    const bbb_lutopt::Ahead a = h->ahead;
+    h->ahead.first += a.n; h->ahead.step += a.n;
+    h->ahead.win_lo += a.n;
+    h->ahead.valid = --h->ahead.left > 0;
+    return a;
 }
 
 // deliver bytes [win_lo, win_lo + n) of the stream staged in `slot` (partition L, G, nlanes) to dst
@@ -532,7 +601,7 @@ int deliver_i8(bbb_lutopt *h, int slot, void *dst, uint64_t win_lo, uint64_t n, 
     });
 }
 
-// produce: the sample kernel for the stream positions the planes in h->d_planes describe, L steps per generator, into the
+// produce: the sample kernel for the stream positions the planes in h->cur describe, L steps per generator, into the
 // next staging slot.  planes_seeded_after_mover: the start states came from a prefetch whose seeding had itself waited for
 // the mover that last read this slot (bbb_awgn_prefetch on a staged handle), so the arithmetic need not wait for it again.
 int produce_planes(bbb_lutopt *h, uint64_t L, unsigned nlanes, bbb_lutopt::ProfEv *ev, bool planes_seeded_after_mover, int *slot_out,
@@ -541,13 +610,11 @@ int produce_planes(bbb_lutopt *h, uint64_t L, unsigned nlanes, bbb_lutopt::ProfE
     const int slot = h->stage_slot ^= 1;
     *slot_out = slot;
     if (h->ahead.valid && h->ahead.slot == slot) h->ahead.valid = false;            // what waited there is overwritten now
-    for (hipEvent_t *e : {&h->stage_free[slot], &h->stage_arith[slot]})
-        if (!*e) BBB_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
-    if (h->stage_cap[slot] < need_words) {
+    int rc;
+    if (h->d_stage[slot].cap < need_words) {
         if (h->stage_busy[slot]) BBB_HIP(hipEventSynchronize(h->stage_free[slot]));     // growing frees the old buffer
         h->stage_busy[slot] = false;
-        int rc = grow(&h->d_stage[slot], &h->stage_cap[slot], need_words);
-        if (rc) return rc;
+        if ((rc = h->d_stage[slot].grow(need_words))) return rc;
     }
     // (the skip holds only while no LATER mover was queued on the slot: a prefetch stays valid across fills that do not
     // match it, and those may have put new movers on this very slot since its seeding waited)
@@ -557,13 +624,12 @@ int produce_planes(bbb_lutopt *h, uint64_t L, unsigned nlanes, bbb_lutopt::ProfE
     if (h->stage_busy[slot] && !seeding_saw_last_mover)
         BBB_HIP(hipStreamWaitEvent(h->cs, h->stage_free[slot], 0));   // its last mover has read it
     if (ev) BBB_HIP(hipEventRecord(ev->e1, h->cs));
-    int rc = awgn256_planes_launch(h->d_planes, (void *)h->d_stage[slot], (unsigned)L, nlanes, h->cs, small_footprint);
+    rc = awgn256_planes_launch(h->cur.buf[kPlanes], (void *)h->d_stage[slot].p, (unsigned)L, nlanes, h->cs, small_footprint);
     h->last_staged_small = small_footprint;
     if (rc) return rc;
     if ((rc = mark_planes_read(h))) return rc;
     if (ev) BBB_HIP(hipEventRecord(ev->e2, h->cs));
-    BBB_HIP(hipEventRecord(h->stage_arith[slot], h->cs));
-    return BBB_OK;
+    return h->stage_arith[slot].record(h->cs);
 }
 
 // the packed n512 kernel's partition: 16 generators per lane, 1024 per wave, segments in multiples of 8 samples (16-byte
@@ -597,25 +663,8 @@ int awgn_fill(bbb_lutopt *h, void *dst, int elem_size, uint64_t nsamples, uint64
         int rc5 = begin_op(h, false);
         if (rc5) return rc5;
         h->planes_valid = false;                 // (another layout than the one prepare_planes caches)
-        if (h->pf.valid && h->pf.first == first_step && h->pf.L == L && h->pf.G == G) {
-            // announced (bbb_awgn_prefetch): the start states were seeded on the side stream -- swap them in
-            BBB_HIP(hipStreamWaitEvent(h->cs, h->pf.seeded, 0));
-            std::swap(h->d_states, h->pf.d_states); std::swap(h->states_cap, h->pf.states_cap);
-            std::swap(h->d_planes, h->pf.d_planes); std::swap(h->planes_cap, h->pf.planes_cap);
-            std::swap(h->cur_last_read, h->pf.last_read); std::swap(h->cur_read_pending, h->pf.read_pending);
-            h->pf.valid = false;
-        } else {
-            JumpPlan *plan;
-            if ((rc5 = get_plan(h, L, &plan))) return rc5;
-            if ((rc5 = grow(&h->d_states, &h->states_cap, (size_t)G * h->W32))) return rc5;
-            if ((rc5 = grow(&h->d_planes, &h->planes_cap, (size_t)2 * h->k * nlanes))) return rc5;
-            uint64_t s0[8];
-            h->pw->apply(first_step, h->init, s0);
-            uint32_t s16[256];
-            first16(*plan, s0, s16);
-            if ((rc5 = awgn_seed_launch(h->k, plan->d_cols, s16, G, h->d_states, G, nlanes, h->d_planes, h->cs, 1))) return rc5;
-        }
-        if ((rc5 = awgn512p_fill_launch(h->d_planes, (int16_t *)dst, nsamples, (unsigned)L, G, nlanes, h->cs))) return rc5;
+        if ((rc5 = acquire_planes(h, first_step, L, G, nlanes, true, nullptr, 1))) return rc5;
+        if ((rc5 = awgn512p_fill_launch(h->cur.buf[kPlanes], (int16_t *)dst, nsamples, (unsigned)L, G, nlanes, h->cs))) return rc5;
         return mark_planes_read(h);
     }
     partition(h, nsamples, 16, &L, &G, &nlanes);
@@ -633,10 +682,7 @@ int awgn_fill(bbb_lutopt *h, void *dst, int elem_size, uint64_t nsamples, uint64
             int rc0 = begin_op(h, true);
             if (rc0) return rc0;
         }
-        const bbb_lutopt::Ahead a = h->ahead;
-        h->ahead.first += nsamples; h->ahead.step += nsamples;
-        h->ahead.win_lo += nsamples;
-        h->ahead.valid = --h->ahead.left > 0;
+        const bbb_lutopt::Ahead a = take_ahead(h);
         return deliver_i8(h, a.slot, dst, a.win_lo, nsamples, a.L, a.G, a.nlanes);
     }
     const uint64_t m = (uint64_t)h->staged_level;
@@ -653,7 +699,7 @@ int awgn_fill(bbb_lutopt *h, void *dst, int elem_size, uint64_t nsamples, uint64
     const bool small_form = staged && (h->staged_level == 1 || env_knob("BBB_EXP_NOISE_SMALL", 0));
     const uint64_t seed_step = first_step + (small_form ? 1 : 0);
     // (a fill that will take the announced start states does not depend on the previous sample kernel: see begin_op)
-    const bool takes_prefetch = fast256 && h->pf.valid && h->pf.first == seed_step && h->pf.L == L && h->pf.G == G;
+    const bool takes_prefetch = fast256 && h->pf.matches(seed_step, L, G);
     int rc = begin_op(h, staged, staged && takes_prefetch);
     if (rc) return rc;
     bbb_lutopt::ProfEv ev{};
@@ -679,7 +725,7 @@ int awgn_fill(bbb_lutopt *h, void *dst, int elem_size, uint64_t nsamples, uint64
     }
     if (fast256) {
         if (h->profiling) BBB_HIP(hipEventRecord(ev.e1, h->cs));
-        rc = awgn256_fill_launch(h->d_planes, (int8_t *)dst, nsamples, (unsigned)L, G, nlanes, h->cs);
+        rc = awgn256_fill_launch(h->cur.buf[kPlanes], (int8_t *)dst, nsamples, (unsigned)L, G, nlanes, h->cs);
         if (!rc) rc = mark_planes_read(h);
         if (h->profiling) {
             BBB_HIP(hipEventRecord(ev.e2, h->cs));
@@ -689,16 +735,16 @@ int awgn_fill(bbb_lutopt *h, void *dst, int elem_size, uint64_t nsamples, uint64
     }
     if (h->profiling) { (void)hipEventDestroy(ev.e0); (void)hipEventDestroy(ev.e1); (void)hipEventDestroy(ev.e2); }
     if (h->custom_fill && elem_size == 1) {
-        const int e = h->custom_fill(h->d_planes, (int8_t *)dst, nsamples, (uint32_t)L, G, nlanes, (void *)h->cs);
+        const int e = h->custom_fill(h->cur.buf[kPlanes], (int8_t *)dst, nsamples, (uint32_t)L, G, nlanes, (void *)h->cs);
         if (e) return fail(BBB_EHIP, std::string("custom sample kernel: ") + hipGetErrorString((hipError_t)e));
         return mark_planes_read(h);
     }
     if (h->small_fast && elem_size == 1) {
-        rc = awgn_small_fill_launch(h->small_fast, h->d_planes, (int8_t *)dst, nsamples, (unsigned)L, G, nlanes, h->cs);
+        rc = awgn_small_fill_launch(h->small_fast, h->cur.buf[kPlanes], (int8_t *)dst, nsamples, (unsigned)L, G, nlanes, h->cs);
         return rc ? rc : mark_planes_read(h);
     }
     h->planes_valid = false;    // the table-driven kernel advances the planes in place
-    rc = awgn_generic_fill_launch(h->k, h->d_taps, h->d_row_off, h->d_planes, dst, elem_size, nsamples, (unsigned)L, G,
+    rc = awgn_generic_fill_launch(h->k, h->d_taps, h->d_row_off, h->cur.buf[kPlanes], dst, elem_size, nsamples, (unsigned)L, G,
                                   nlanes, h->cs);
     return rc ? rc : mark_planes_read(h);
 }
@@ -728,6 +774,28 @@ int channel_thresholds(int amp, int noise_var, TrialDev *t) {
     return BBB_OK;
 }
 
+// a trial setting checked and tabulated for the kernels (its L, G and nbits are the caller's)
+int trial_dev(const bbb_trial_cfg &c, TrialDev *t) {
+    const int tap = prbs_tap(c.prbs_k);
+    if (!tap) return fail(BBB_EINVAL, "k=" + std::to_string(c.prbs_k) + " invalid for PRBS");
+    if (c.prbs_state == 0 || (c.prbs_state >> c.prbs_k)) return fail(BBB_EINVAL, "PRBS state must be in [1, 2^k)");
+    if (c.amp < 0 || c.amp > 2047 || c.noise_var < 0 || c.noise_var > 15) return fail(BBB_EINVAL, "amp must be 0..2047 and noise_var 0..15");
+    t->prbs_k = c.prbs_k;
+    t->prbs_tap = tap;
+    return channel_thresholds(c.amp, c.noise_var, t);
+}
+
+// one decision threshold per bit value, strictly inside (0, 256): only such settings can share a launch (the straight-line
+// kernel); 12-bit wrap-around settings run alone on the general kernel
+bool single_threshold(const TrialDev &t) {
+    for (int bv = 0; bv < 2; bv++) {
+        int real = 0;
+        for (int j = 0; j < t.nthr[bv]; j++) real += t.thr[bv][j] > 0 && t.thr[bv][j] < 256;
+        if (real != 1) return false;
+    }
+    return true;
+}
+
 int ber_run(bbb_lutopt *h, const bbb_trial_cfg *cfgs, int ncfg, unsigned long long *counters_dev) {
     {
         const int rc0 = begin_op(h, false);
@@ -739,16 +807,9 @@ int ber_run(bbb_lutopt *h, const bbb_trial_cfg *cfgs, int ncfg, unsigned long lo
     std::vector<TrialDev> td((size_t)ncfg);
     for (int i = 0; i < ncfg; i++) {
         const bbb_trial_cfg &c = cfgs[i];
-        const int tap = prbs_tap(c.prbs_k);
-        if (!tap) return fail(BBB_EINVAL, "k=" + std::to_string(c.prbs_k) + " invalid for PRBS");
-        if (c.prbs_state == 0 || (c.prbs_state >> c.prbs_k)) return fail(BBB_EINVAL, "PRBS state must be in [1, 2^k)");
-        if (c.amp < 0 || c.amp > 2047 || c.noise_var < 0 || c.noise_var > 15)
-            return fail(BBB_EINVAL, "amp must be 0..2047 and noise_var 0..15");
         if (c.warmup + c.first_bit < c.warmup || c.warmup + c.first_bit + c.nbits < c.nbits)
             return fail(BBB_EINVAL, "warmup + first_bit + nbits overflows");
-        td[(size_t)i].prbs_k = c.prbs_k;
-        td[(size_t)i].prbs_tap = tap;
-        int rc = channel_thresholds(c.amp, c.noise_var, &td[(size_t)i]);
+        const int rc = trial_dev(c, &td[(size_t)i]);
         if (rc) return rc;
     }
     // Consecutive trials that read the SAME noise and PRBS streams (same seeds, offsets, length)
@@ -756,22 +817,11 @@ int ber_run(bbb_lutopt *h, const bbb_trial_cfg *cfgs, int ncfg, unsigned long lo
     // streams.  The counters are identical to running them one by one.
     for (int i = 0; i < ncfg;) {
         const bbb_trial_cfg &c = cfgs[i];
-        // only settings with one decision threshold per bit value can share a launch (the
-        // straight-line kernel); 12-bit wrap-around settings run alone on the general kernel
-        auto single = [&](int idx) {
-            const TrialDev &t = td[(size_t)idx];
-            for (int bv = 0; bv < 2; bv++) {
-                int real = 0;                       // thresholds strictly inside (0, 256)
-                for (int j = 0; j < t.nthr[bv]; j++) real += t.thr[bv][j] > 0 && t.thr[bv][j] < 256;
-                if (real != 1) return false;
-            }
-            return true;
-        };
         int n = 1;
-        while (single(i) && i + n < ncfg && n < BBB_BER_MAX_GROUP) {
+        while (single_threshold(td[(size_t)i]) && i + n < ncfg && n < BBB_BER_MAX_GROUP) {
             const bbb_trial_cfg &d = cfgs[i + n];
             if (d.prbs_k != c.prbs_k || d.prbs_state != c.prbs_state || d.warmup != c.warmup ||
-                d.first_bit != c.first_bit || d.nbits != c.nbits || !single(i + n))
+                d.first_bit != c.first_bit || d.nbits != c.nbits || !single_threshold(td[(size_t)(i + n)]))
                 break;
             n++;
         }
@@ -784,7 +834,7 @@ int ber_run(bbb_lutopt *h, const bbb_trial_cfg *cfgs, int ncfg, unsigned long lo
         for (int j = 0; j < n; j++) { td[(size_t)(i + j)].L = (uint32_t)L; td[(size_t)(i + j)].G = G; td[(size_t)(i + j)].nbits = c.nbits; }
         int rc;
         // The BER kernels take the state OF their first sample: one clock past the stream position.  Neither set of start states
-        // touches the handle's stream-fill buffers (d_states / d_planes, the prefetch set): trials own two pairs of generator buffers
+        // touches the handle's stream-fill buffers (cur, the prefetch set): trials own two pairs of generator buffers
         // (the first 65536 states packed + the bit planes) and two PRBS pairs, each taken in turn.
         //
         // Round 5 (profiles/r05_base_ber_timeline.txt: an isolated trial's kernel started 155 us after the first launch -- seven
@@ -807,14 +857,8 @@ int ber_run(bbb_lutopt *h, const bbb_trial_cfg *cfgs, int ncfg, unsigned long lo
         JumpPlan *pp, *plan = nullptr;
         if ((rc = get_prbs_plan(h, c.prbs_k, L, &pp))) return rc;
         const int pb = h->pp_idx ^= 1;
-        for (int b : {pb, pb ^ 1}) {               // (both pairs sized by the first trial of a size: an allocation sits in the call's path)
-            if (!h->pp_read[b]) BBB_HIP(hipEventCreateWithFlags(&h->pp_read[b], hipEventDisableTiming));
-            if (h->pplanes_cap[b] < (size_t)32 * nlanes) {
-                if (h->pp_pending[b]) BBB_HIP(hipEventSynchronize(h->pp_read[b]));          // growing frees the old buffer
-                h->pp_pending[b] = false;
-                if ((rc = grow(&h->d_pplanes[b], &h->pplanes_cap[b], (size_t)32 * nlanes))) return rc;
-            }
-        }
+        for (int b : {pb, pb ^ 1})                 // (both pairs sized by the first trial of a size: an allocation sits in the call's path)
+            if ((rc = h->pp[b].grow({(size_t)32 * nlanes}))) return rc;
         uint32_t ps16[256], s16[256];
         {
             uint64_t ps0 = 0;
@@ -829,36 +873,32 @@ int ber_run(bbb_lutopt *h, const bbb_trial_cfg *cfgs, int ncfg, unsigned long lo
         if (seed_gen) {
             sb = h->bs_idx ^= 1;
             for (int b : {sb, sb ^ 1}) {
-                if (!h->bs_read[b]) BBB_HIP(hipEventCreateWithFlags(&h->bs_read[b], hipEventDisableTiming));
-                if (h->bstates_cap[b] < (size_t)65536 * h->W32 || h->bplanes_cap[b] < (size_t)h->k * nlanes) {
+                if (h->d_bstates[b].cap < (size_t)65536 * h->W32 || h->d_bplanes[b].cap < (size_t)h->k * nlanes) {
                     if (h->bs_pending[b]) BBB_HIP(hipEventSynchronize(h->bs_read[b]));      // growing frees the old buffers
                     h->bs_pending[b] = false;
                     h->bs_valid[b] = false;
-                    if ((rc = grow(&h->d_bstates[b], &h->bstates_cap[b], (size_t)65536 * h->W32))) return rc;
-                    if ((rc = grow(&h->d_bplanes[b], &h->bplanes_cap[b], (size_t)h->k * nlanes))) return rc;
+                    if ((rc = h->d_bstates[b].grow((size_t)65536 * h->W32))) return rc;
+                    if ((rc = h->d_bplanes[b].grow((size_t)h->k * nlanes))) return rc;
                 }
             }
-            for (int b : {0, 1})
-                if (!h->bs_ready[b]) BBB_HIP(hipEventCreateWithFlags(&h->bs_ready[b], hipEventDisableTiming));
             if ((rc = get_plan(h, L, &plan))) return rc;
             if ((rc = ensure_top_tables(plan))) return rc;
-            uint64_t s0[8] = {0};
-            h->pw->apply(gen_first, h->init, s0);
-            first16(*plan, s0, s16);
+            first16_at(h, *plan, gen_first, s16);
         }
         // -- launches
         const bool busy = seed_gen && hipStreamQuery(h->cs) == hipErrorNotReady;
         hipStream_t ss = busy ? h->xs2[0] : h->cs;
+        ReadGuarded<1> &prbs = h->pp[pb];
         // (the PRBS pair's last reader, the trial before last: wherever its seeding goes now)
-        if (h->pp_pending[pb]) BBB_HIP(hipStreamWaitEvent(seed_gen ? ss : h->cs, h->pp_read[pb], 0));
+        if ((rc = prbs.wait_read(seed_gen ? ss : h->cs))) return rc;
         if (seed_gen) {
             h->bs_valid[sb] = false;
             if (h->bs_pending[sb]) BBB_HIP(hipStreamWaitEvent(ss, h->bs_read[sb], 0));    // the trial before last read this pair
             // the PRBS start states ride on the head launch (extra blocks: VALU work beside the head's LDS and L2 latency)
-            const PrbsSeedRide ride{c.prbs_k, pp->d_cols, ps16, pp->qcol64, nlanes, h->d_pplanes[pb]};
+            const PrbsSeedRide ride{c.prbs_k, pp->d_cols, ps16, pp->qcol64, nlanes, prbs.buf[0]};
             if ((rc = awgn_seed_head_launch(h->k, plan->d_cols, s16, G, h->d_bstates[sb], ss, &ride))) return rc;
             if ((rc = awgn_seed_tail_planes_launch(h->k, plan->d_top, G, h->d_bstates[sb], nlanes, h->d_bplanes[sb], ss))) return rc;
-            BBB_HIP(hipEventRecord(h->bs_ready[sb], ss));
+            if ((rc = h->bs_ready[sb].record(ss))) return rc;
             if (busy) BBB_HIP(hipStreamWaitEvent(h->cs, h->bs_ready[sb], 0));
             h->bs_valid[sb] = true;
             h->bs_first[sb] = gen_first; h->bs_L[sb] = L; h->bs_G[sb] = G;
@@ -866,17 +906,16 @@ int ber_run(bbb_lutopt *h, const bbb_trial_cfg *cfgs, int ncfg, unsigned long lo
             // the same trial again: its generator states were derived by an earlier call -- on whatever stream that call found right;
             // the PRBS states (their pairs alternate) in line
             BBB_HIP(hipStreamWaitEvent(h->cs, h->bs_ready[sb], 0));
-            if ((rc = prbs_seed_lanes_launch(c.prbs_k, pp->d_cols, ps16, pp->qcol64, G, nlanes, h->d_pplanes[pb], h->cs))) return rc;
+            if ((rc = prbs_seed_lanes_launch(c.prbs_k, pp->d_cols, ps16, pp->qcol64, G, nlanes, prbs.buf[0], h->cs))) return rc;
         }
         if (h->specialised) {
-            if ((rc = ber256_launch(h->d_bplanes[sb], h->d_pplanes[pb], &td[(size_t)i], n, nlanes, counters_dev + 2 * (size_t)i, h->cs))) return rc;
+            if ((rc = ber256_launch(h->d_bplanes[sb], prbs.buf[0], &td[(size_t)i], n, nlanes, counters_dev + 2 * (size_t)i, h->cs))) return rc;
         } else {
-            const int e = h->custom_ber(h->d_bplanes[sb], h->d_pplanes[pb], &td[(size_t)i], n, nlanes, (uint64_t *)(counters_dev + 2 * (size_t)i), (void *)h->cs);
+            const int e = h->custom_ber(h->d_bplanes[sb], prbs.buf[0], &td[(size_t)i], n, nlanes, (uint64_t *)(counters_dev + 2 * (size_t)i), (void *)h->cs);
             if (e) return fail(e < 0 ? e : BBB_EHIP, "custom BER kernel failed");
         }
-        BBB_HIP(hipEventRecord(h->pp_read[pb], h->cs));
-        h->pp_pending[pb] = true;
-        BBB_HIP(hipEventRecord(h->bs_read[sb], h->cs));
+        if ((rc = prbs.mark_read(h->cs))) return rc;
+        if ((rc = h->bs_read[sb].record(h->cs))) return rc;
         h->bs_pending[sb] = true;
         i += n;
     }
@@ -976,14 +1015,11 @@ int bbb_lutopt_create(bbb_lutopt **out, int k, const uint16_t *taps, const uint3
     h->device = device;
     h->taps.assign(taps, taps + row_off[k]);
     h->row_off.assign(row_off, row_off + k + 1);
-    bool any = false;
-    for (int w = 0; w < h->W64; w++) {
+    for (int w = 0; w < h->W64; w++) {      // (an all-zero state is legal in the HDL too: it just stays zero)
         uint64_t v = init_words[w];
         if (w == h->W64 - 1 && (k & 63)) v &= (1ull << (k & 63)) - 1ull;
         h->init[w] = v;
-        any |= v != 0;
     }
-    (void)any;   // an all-zero state is legal in the HDL too (it just stays zero)
     h->pw.reset(new GF2Powers(A));
     h->specialised = awgn256_matches(k, taps, row_off);
     h->small_fast = awgn_small_matches(k, taps, row_off);
@@ -995,10 +1031,10 @@ int bbb_lutopt_create(bbb_lutopt **out, int k, const uint16_t *taps, const uint3
     hipDeviceProp_t p;
     BBB_HIP(hipGetDeviceProperties(&p, device));
     h->max_waves = (unsigned)p.multiProcessorCount * 4;    // one wave per SIMD
-    BBB_HIP(hipMalloc((void **)&h->d_taps, sizeof(uint16_t) * h->taps.size()));
-    BBB_HIP(hipMalloc((void **)&h->d_row_off, sizeof(uint32_t) * h->row_off.size()));
-    BBB_HIP(hipMemcpy(h->d_taps, h->taps.data(), sizeof(uint16_t) * h->taps.size(), hipMemcpyHostToDevice));
-    BBB_HIP(hipMemcpy(h->d_row_off, h->row_off.data(), sizeof(uint32_t) * h->row_off.size(), hipMemcpyHostToDevice));
+    int rc = h->d_taps.grow(h->taps.size());
+    if (rc || (rc = h->d_row_off.grow(h->row_off.size()))) return rc;
+    BBB_HIP(hipMemcpy(h->d_taps.p, h->taps.data(), sizeof(uint16_t) * h->taps.size(), hipMemcpyHostToDevice));
+    BBB_HIP(hipMemcpy(h->d_row_off.p, h->row_off.data(), sizeof(uint32_t) * h->row_off.size(), hipMemcpyHostToDevice));
     *out = h.release();
     return BBB_OK;
 }
@@ -1008,26 +1044,12 @@ int bbb_lutopt_destroy(bbb_lutopt *h) {
     if (h->device < 0) { delete h; return BBB_OK; }
     (void)hipSetDevice(h->device);
     (void)hipDeviceSynchronize();
-    for (auto &p : h->plans) { (void)hipFree(p.second.d_cols); if (p.second.d_top) (void)hipFree(p.second.d_top); }
-    for (auto &p : h->prbs_plans) (void)hipFree(p.second.d_cols);
-    for (void *p : {(void *)h->d_states, (void *)h->d_planes, (void *)h->d_pstates[0], (void *)h->d_pplanes[0], (void *)h->d_pstates[1], (void *)h->d_pplanes[1],
-                    (void *)h->d_taps, (void *)h->d_row_off, (void *)h->d_counters, (void *)h->d_txnoise,
-                    (void *)h->d_txbits, (void *)h->d_fbits[0], (void *)h->d_fbits[1], (void *)h->d_mbits[0][0], (void *)h->d_mbits[0][1], (void *)h->d_mbits[1][0], (void *)h->d_mbits[1][1], (void *)h->pf.d_states, (void *)h->pf.d_planes,
-                    (void *)h->d_bstates[0], (void *)h->d_bstates[1], (void *)h->d_bplanes[0], (void *)h->d_bplanes[1]})
-        (void)hipFree(p);
-    if (h->h_counters) (void)hipHostFree(h->h_counters);
-    for (hipEvent_t e : {h->pf.seeded, h->pf.last_read, h->cur_last_read, h->handover, h->stage_free[0], h->stage_free[1],
-                         h->stage_arith[0], h->stage_arith[1], h->ev_user, h->fbits_read[0], h->fbits_read[1], h->fbits_ready, h->ber_join, h->pp_read[0], h->pp_read[1],
-                         h->bs_read[0], h->bs_read[1], h->bs_ready[0], h->bs_ready[1], h->counters_zeroed})
-        if (e) (void)hipEventDestroy(e);
     // (profiling events of calls whose times were never read: found by the scheduler model's leak check, tests/sched_model)
     for (auto &pr : h->prof_mover_pending) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
     for (auto &ev : h->prof_pending) { (void)hipEventDestroy(ev.e0); (void)hipEventDestroy(ev.e1); (void)hipEventDestroy(ev.e2); }
     if (h->prof_prev_e2) (void)hipEventDestroy(h->prof_prev_e2);
     if (h->ys) (void)hipStreamDestroy(h->ys);        // (the other internal streams are the device's pool: ensure_internal_streams)
-    (void)hipFree(h->d_stage[0]);
-    (void)hipFree(h->d_stage[1]);
-    delete h;
+    delete h;                                        // (its members free the device buffers and destroy the events)
     return BBB_OK;
 }
 
@@ -1157,18 +1179,12 @@ static int seed_announced(bbb_lutopt *h, uint64_t first_step, uint64_t L, uint64
     if (pf.seeded) BBB_HIP(hipStreamWaitEvent(side, pf.seeded, 0));
     else BBB_HIP(hipEventCreateWithFlags(&pf.seeded, hipEventDisableTiming));
     // the buffers may still be read by the sample kernel that used them last (main stream)
-    if (pf.read_pending) BBB_HIP(hipStreamWaitEvent(side, pf.last_read, 0));
-    if (pf.states_cap < (size_t)G * h->W32 || pf.planes_cap < (size_t)2 * h->k * nlanes) {
-        if (pf.read_pending) BBB_HIP(hipEventSynchronize(pf.last_read));     // growing frees the old buffers
-        if ((rc = grow(&pf.d_states, &pf.states_cap, (size_t)G * h->W32))) return rc;
-        if ((rc = grow(&pf.d_planes, &pf.planes_cap, (size_t)2 * h->k * nlanes))) return rc;
-    }
-    pf.read_pending = false;
-    uint64_t s0[8] = {0};
-    h->pw->apply(first_step, h->init, s0);
+    if ((rc = pf.set.wait_read(side))) return rc;
+    if ((rc = pf.set.grow({(size_t)G * h->W32, (size_t)2 * h->k * nlanes}))) return rc;
+    pf.set.read_pending = false;          // (that reader is in front of the seeding now)
     uint32_t s16[256];
-    first16(*plan, s0, s16);
-    if ((rc = awgn_seed_launch(h->k, plan->d_cols, s16, G, pf.d_states, G, nlanes, pf.d_planes, side, h->fast512 ? 1 : 0, seed_variant))) return rc;
+    first16_at(h, *plan, first_step, s16);
+    if ((rc = awgn_seed_launch(h->k, plan->d_cols, s16, G, pf.set.buf[kStates], G, nlanes, pf.set.buf[kPlanes], side, h->fast512 ? 1 : 0, seed_variant))) return rc;
     BBB_HIP(hipEventRecord(pf.seeded, side));
     pf.valid = true;
     pf.first = first_step; pf.L = L; pf.G = G; pf.nlanes = nlanes;
@@ -1217,7 +1233,7 @@ static int awgn_prefetch(bbb_lutopt *h, uint64_t nsamples, uint64_t first_step, 
         partition(h, nsamples, 16, &L, &G, &nlanes);
     }
     if (L > 0xffffff00ull) return BBB_OK;                         // the matching fill will refuse; nothing to prepare
-    if (h->pf.valid && h->pf.first == first_step && h->pf.L == L && h->pf.G == G) return BBB_OK;      // already under way
+    if (h->pf.matches(first_step, L, G)) return BBB_OK;      // already under way
     // Which stream seeds.  A staged k = 256 handle: the ARITHMETIC stream of the staging slot the announced fill will take --
     // the sample kernel then follows its start states on one stream, with no event between them.  (With the seeding on a
     // stream of its own beside two arithmetic streams the mover and the seeding ran BETWEEN the sample kernels instead of
@@ -1254,10 +1270,10 @@ int bbb_awgn_fill_i16(bbb_lutopt *h, int16_t *dst_dev, uint64_t nsamples, uint64
     if (h && h->specialised && h->device >= 0 && nsamples && dst_dev && !((uintptr_t)dst_dev & 15) && (nsamples % 16) == 0) {
         // the generated k = 256 kernel writes int8: fill a scratch buffer with it, then sign-extend
         BBB_HIP(hipSetDevice(h->device));
-        int rc = grow(&h->d_txnoise, &h->txnoise_cap, (size_t)(nsamples + 15) / 4 + 4);
+        int rc = h->d_txnoise.grow((size_t)(nsamples + 15) / 4 + 4);
         if (rc) return rc;
         if ((rc = awgn_fill(h, h->d_txnoise, 1, nsamples, first_step))) return rc;
-        return widen_i8_i16_launch((const int8_t *)h->d_txnoise, dst_dev, nsamples, h->stream);
+        return widen_i8_i16_launch((const int8_t *)h->d_txnoise.p, dst_dev, nsamples, h->stream);
     }
     return awgn_fill(h, dst_dev, 2, nsamples, first_step);
 }
@@ -1357,11 +1373,11 @@ int bbb_lutopt_fill_words(bbb_lutopt *h, uint32_t *dst_dev, uint64_t nstates, ui
     rc = prepare_planes(h, first_step, L, G, nlanes);
     if (rc) return rc;
     if (fast) {        // the shipped n256 matrix: generated network, planes stay valid (not advanced in place)
-        rc = lutopt_words256_launch(h->d_planes, dst_dev, nstates, (unsigned)L, G, nlanes, msb_first != 0, h->cs);
+        rc = lutopt_words256_launch(h->cur.buf[kPlanes], dst_dev, nstates, (unsigned)L, G, nlanes, msb_first != 0, h->cs);
         return rc ? rc : mark_planes_read(h);
     }
     h->planes_valid = false;    // the table-driven kernel advances the planes in place
-    rc = lutopt_words_launch(h->k, h->d_taps, h->d_row_off, h->d_planes, dst_dev, nstates, (unsigned)L, G, nlanes,
+    rc = lutopt_words_launch(h->k, h->d_taps, h->d_row_off, h->cur.buf[kPlanes], dst_dev, nstates, (unsigned)L, G, nlanes,
                              msb_first != 0, h->cs);
     if (!rc) rc = mark_planes_read(h);
     return rc;
@@ -1544,10 +1560,9 @@ int bbb_tx_fill_i16(bbb_lutopt *h, const bbb_tx_cfg *cfg, int16_t *out_dev, uint
                 // the slot's OTHER buffer than last time: its readers were the movers of the slot's kernel before last; the slot's last
                 // kernel waited for them (stage_free stands for every mover of the slot so far) and was queued on this stream
                 bits_buf = h->mbits_turn[slot] ^= 1u;
-                if (h->mbits_cap[slot][bits_buf] < (size_t)words64 * 2) {
+                if (h->d_mbits[slot][bits_buf].cap < (size_t)words64 * 2) {
                     if (h->stage_busy[slot]) BBB_HIP(hipEventSynchronize(h->stage_free[slot]));      // growing frees the old buffer
-                    int rcg = grow(&h->d_mbits[slot][bits_buf], &h->mbits_cap[slot][bits_buf], (size_t)words64 * 2);
-                    if (rcg) return rcg;
+                    if (const int rcg = h->d_mbits[slot][bits_buf].grow((size_t)words64 * 2)) return rcg;
                 }
                 d_bits = h->d_mbits[slot][bits_buf];
                 if (!cfg->bit_en || !nbits_all) return BBB_OK;
@@ -1569,14 +1584,11 @@ int bbb_tx_fill_i16(bbb_lutopt *h, const bbb_tx_cfg *cfg, int16_t *out_dev, uint
                 tx_cfg_equal(h->ahead.cfg, *cfg)) {
                 // (no begin_op: see awgn_fill's look-ahead delivery)
                 if (env_knob("BBB_EXP_DELIVER_HANDOVER", 0) && (rc = begin_op(h, true))) return rc;
-                const bbb_lutopt::Ahead a = h->ahead;
+                const bbb_lutopt::Ahead a = take_ahead(h);
                 // its data bits sit in the slot's buffer, behind those of the windows before it
                 d_bits = h->d_mbits[a.slot][a.bits_buf]; words64 = a.bits_words64;
                 rel = (uint32_t)(FM - 7 - (a.bits_m0 - 128));
                 bits_on = cfg->bit_en != 0;
-                h->ahead.first += nsamples; h->ahead.step += nsamples;
-                h->ahead.win_lo += nsamples;
-                h->ahead.valid = --h->ahead.left > 0;
                 return deliver_tx(a.slot, a.win_lo, a.L, a.G, a.nlanes);
             }
             const uint64_t mla = (uint64_t)h->staged_level;
@@ -1588,7 +1600,7 @@ int bbb_tx_fill_i16(bbb_lutopt *h, const bbb_tx_cfg *cfg, int16_t *out_dev, uint
             if (L > 0xffffff00ull) return fail(BBB_EINVAL, "nsamples too large for one call (segment length must fit 32 bits): split it");
             const uint64_t step0 = cfg->warmup + first_sample;                // tx.py:70-71
             const uint64_t seed_step = step0 + 1;      // (the small form of the noise kernel is given the state OF its first sample)
-            const bool takes_prefetch = h->pf.valid && h->pf.first == seed_step && h->pf.L == L && h->pf.G == G;
+            const bool takes_prefetch = h->pf.matches(seed_step, L, G);
             if ((rc = begin_op(h, true, takes_prefetch))) return rc;
             h->last_fill_tx = false;            // (what runs on the SIMDs is the plain kernel)
             bool from_pf = false;
@@ -1622,47 +1634,38 @@ int bbb_tx_fill_i16(bbb_lutopt *h, const bbb_tx_cfg *cfg, int16_t *out_dev, uint
         const uint64_t words64 = 2 + (nbits + 63) / 64 + (L / 8 + 63) / 64 + 2;
         const int bs = h->fbits_slot ^= 1;
         { const int rcs_ = ensure_side_stream(h); if (rcs_) return rcs_; }
-        for (hipEvent_t *e : {&h->fbits_read[bs], &h->fbits_ready})
-            if (!*e) BBB_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
-        if (h->fbits_cap[bs] < (size_t)words64 * 2) {
-            if (h->fbits_pending[bs]) BBB_HIP(hipEventSynchronize(h->fbits_read[bs]));      // growing frees the old buffer
-            h->fbits_pending[bs] = false;
-            if ((rc = grow(&h->d_fbits[bs], &h->fbits_cap[bs], (size_t)words64 * 2))) return rc;
-        }
-        uint32_t *const d_bits = h->d_fbits[bs];
+        ReadGuarded<1> &fb = h->fbits[bs];
+        if ((rc = fb.grow({(size_t)words64 * 2}))) return rc;
+        uint32_t *const d_bits = fb.buf[0];
         if (use_bits) {
             // on the side stream: not behind the previous call's sample kernel, which is what h->cs would mean
-            if (h->fbits_pending[bs]) BBB_HIP(hipStreamWaitEvent(h->side, h->fbits_read[bs], 0));
+            if ((rc = fb.wait_read(h->side))) return rc;
             BBB_HIP(hipMemsetAsync(d_bits, 0, 16, h->side));
             uint64_t *bits64 = (uint64_t *)d_bits + 2;
             if (cfg->source == 0) rc = prbs_fill_launch(cfg->prbs_k, cfg->prbs_state, (uint64_t)m0, nbits, bits64, h->side);
             else rc = pulse_bits_launch(bits64, m0, (nbits + 63) / 64, h->side);
-            if (rc) return rc;
-            BBB_HIP(hipEventRecord(h->fbits_ready, h->side));
+            if (rc || (rc = h->fbits_ready.record(h->side))) return rc;
             BBB_HIP(hipStreamWaitEvent(h->cs, h->fbits_ready, 0));
         }
         if ((rc = acquire_planes(h, cfg->warmup + first_sample, L, G, nlanes, true))) return rc;      // tx.py:70-71
-        rc = awgn256_tx_launch(h->d_planes, out_dev, nsamples, (unsigned)L, G, nlanes, cfg->coeffs, d_bits, (uint32_t)(words64 * 2), rel_base,
+        rc = awgn256_tx_launch(h->cur.buf[kPlanes], out_dev, nsamples, (unsigned)L, G, nlanes, cfg->coeffs, d_bits, (uint32_t)(words64 * 2), rel_base,
                                (uint32_t)(F & 7), cfg->noise_var, cfg->bit_en, use_bits ? 1 : 0, h->cs);
         if (!rc) rc = mark_planes_read(h);
-        if (rc) return rc;
-        BBB_HIP(hipEventRecord(h->fbits_read[bs], h->cs));            // the fused kernel is the last reader of the data bits
-        h->fbits_pending[bs] = true;
-        return BBB_OK;
+        return rc ? rc : fb.mark_read(h->cs);            // the fused kernel is the last reader of the data bits
     }
     if ((rc = begin_op(h, false))) return rc;
     tx_bit_range(first_sample, nsamples, &m0, &nbits);
     const bool have_bits = cfg->source == 0 && nbits && cfg->bit_en;
     if (have_bits) {
-        if ((rc = grow(&h->d_txbits, &h->txbits_cap, (size_t)((nbits + 63) / 64 + 2) * 2))) return rc;
-        if ((rc = prbs_fill_launch(cfg->prbs_k, cfg->prbs_state, (uint64_t)m0, nbits, (uint64_t *)h->d_txbits, h->stream))) return rc;
+        if ((rc = h->d_txbits.grow((size_t)((nbits + 63) / 64 + 2) * 2))) return rc;
+        if ((rc = prbs_fill_launch(cfg->prbs_k, cfg->prbs_state, (uint64_t)m0, nbits, (uint64_t *)h->d_txbits.p, h->stream))) return rc;
     }
     if (cfg->noise_en) {
-        if ((rc = grow(&h->d_txnoise, &h->txnoise_cap, (size_t)(nsamples + 15) / 4 + 4))) return rc;
+        if ((rc = h->d_txnoise.grow((size_t)(nsamples + 15) / 4 + 4))) return rc;
         if ((rc = awgn_fill(h, h->d_txnoise, 1, nsamples, cfg->warmup + first_sample))) return rc;   // tx.py:70-71
     }
-    return tx_waveform_launch(cfg->coeffs, have_bits ? (const uint64_t *)h->d_txbits : nullptr, m0, have_bits ? nbits : 0,
-                              cfg->bit_en ? cfg->source : 1, (const int8_t *)h->d_txnoise, cfg->noise_var, cfg->bit_en,
+    return tx_waveform_launch(cfg->coeffs, have_bits ? (const uint64_t *)h->d_txbits.p : nullptr, m0, have_bits ? nbits : 0,
+                              cfg->bit_en ? cfg->source : 1, (const int8_t *)h->d_txnoise.p, cfg->noise_var, cfg->bit_en,
                               cfg->noise_en, first_sample, nsamples, out_dev, h->stream);
 }
 
@@ -1799,24 +1802,10 @@ int bbb_ber_trials_dev(bbb_lutopt *h, const bbb_trial_cfg *cfgs, int ncfg, uint6
 
 // the handle's device counters and their pinned host mirror (a pageable read-back goes through the runtime's staging buffer)
 static int ensure_counters(bbb_lutopt *h, size_t need) {
-    if (h->counters_cap < need) {
-        if (h->d_counters) BBB_HIP(hipFree(h->d_counters));
-        h->d_counters = nullptr;
-        h->counters_cap = 0;
-        const size_t cap = need < 64 ? 64 : need;
-        BBB_HIP(hipMalloc((void **)&h->d_counters, cap * sizeof(unsigned long long)));
-        h->counters_cap = cap;
-        h->counters_clean = false;
-    }
-    if (h->h_counters_cap < need) {
-        if (h->h_counters) BBB_HIP(hipHostFree(h->h_counters));
-        h->h_counters = nullptr;
-        h->h_counters_cap = 0;
-        const size_t cap = need < 64 ? 64 : need;
-        BBB_HIP(hipHostMalloc((void **)&h->h_counters, cap * sizeof(unsigned long long), hipHostMallocDefault));
-        h->h_counters_cap = cap;
-    }
-    return BBB_OK;
+    const size_t cap = need < 64 ? 64 : need;      // (both hold 0 or at least 64: they grow exactly when they hold fewer than need)
+    if (h->d_counters.cap < cap) h->counters_clean = false;
+    int rc = h->d_counters.grow(cap);
+    return rc ? rc : h->h_counters.grow(cap);
 }
 
 // d_counters[0 .. need) zero on h->stream: the zeroing queued behind the previous read-back is taken (its event waited for: the
@@ -1834,9 +1823,8 @@ static int take_clean_counters(bbb_lutopt *h, size_t need) {
 // queues the pinned read-back of d_counters[0 .. need) on h->stream and, behind it, the zeroing for the next call
 static int read_back_counters(bbb_lutopt *h, size_t need) {
     BBB_HIP(hipMemcpyAsync(h->h_counters, h->d_counters, need * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
-    BBB_HIP(hipMemsetAsync(h->d_counters, 0, h->counters_cap * sizeof(unsigned long long), h->stream));
-    if (!h->counters_zeroed) BBB_HIP(hipEventCreateWithFlags(&h->counters_zeroed, hipEventDisableTiming));
-    BBB_HIP(hipEventRecord(h->counters_zeroed, h->stream));
+    BBB_HIP(hipMemsetAsync(h->d_counters, 0, h->d_counters.cap * sizeof(unsigned long long), h->stream));
+    if (const int rc = h->counters_zeroed.record(h->stream)) return rc;
     h->counters_clean = true;
     return BBB_OK;
 }
@@ -1874,10 +1862,9 @@ struct bbb_ber_run {
     uint32_t m = 1, call = 0;
     uint64_t n = 0, block = 0, Lb = 0, G = 0;
     unsigned nlanes = 0;
-    uint32_t *d_states = nullptr, *d_planes = nullptr, *d_pstates = nullptr, *d_pplanes = nullptr;
-    size_t states_cap = 0, planes_cap = 0, pstates_cap = 0, pplanes_cap = 0;
-    unsigned long long *d_totals = nullptr;
-    hipEvent_t fork = nullptr, join = nullptr;
+    DevBuf<uint32_t> d_states, d_planes, d_pplanes;
+    DevBuf<unsigned long long> d_totals;
+    Event fork, join;
 };
 
 int bbb_ber_run_open(bbb_lutopt *h, const bbb_trial_cfg *cfgs, int ncfg, uint32_t calls_per_block, bbb_ber_run **out) {
@@ -1896,20 +1883,11 @@ int bbb_ber_run_open(bbb_lutopt *h, const bbb_trial_cfg *cfgs, int ncfg, uint32_
     r->td.resize((size_t)ncfg);
     for (int i = 0; i < ncfg; i++) {
         const bbb_trial_cfg &c = cfgs[i];
-        const int tap = prbs_tap(c.prbs_k);
-        if (!tap) return fail(BBB_EINVAL, "k=" + std::to_string(c.prbs_k) + " invalid for PRBS");
-        if (c.prbs_state == 0 || (c.prbs_state >> c.prbs_k)) return fail(BBB_EINVAL, "PRBS state must be in [1, 2^k)");
-        if (c.amp < 0 || c.amp > 2047 || c.noise_var < 0 || c.noise_var > 15) return fail(BBB_EINVAL, "amp must be 0..2047 and noise_var 0..15");
         if (c.prbs_k != c0.prbs_k || c.prbs_state != c0.prbs_state || c.warmup != c0.warmup || c.first_bit != c0.first_bit || c.nbits != c0.nbits)
             return fail(BBB_EINVAL, "the settings of a continued trial group must share the PRBS, the offsets and nbits (they read one noise stream)");
-        r->td[(size_t)i].prbs_k = c.prbs_k;
-        r->td[(size_t)i].prbs_tap = tap;
-        int rc = channel_thresholds(c.amp, c.noise_var, &r->td[(size_t)i]);
+        const int rc = trial_dev(c, &r->td[(size_t)i]);
         if (rc) return rc;
-        int real[2] = {0, 0};
-        for (int bv = 0; bv < 2; bv++)
-            for (int j = 0; j < r->td[(size_t)i].nthr[bv]; j++) real[bv] += r->td[(size_t)i].thr[bv][j] > 0 && r->td[(size_t)i].thr[bv][j] < 256;
-        if (ncfg > 1 && (real[0] != 1 || real[1] != 1))
+        if (ncfg > 1 && !single_threshold(r->td[(size_t)i]))
             return fail(BBB_EINVAL, "grouped trials must be single-threshold (a wrap-around setting runs alone)");
     }
     r->m = calls_per_block;
@@ -1919,11 +1897,10 @@ int bbb_ber_run_open(bbb_lutopt *h, const bbb_trial_cfg *cfgs, int ncfg, uint32_
     // segments in multiples of 2 m steps: every call runs an even number of steps of every generator
     partition(h, nblock, 2 * r->m, &r->Lb, &r->G, &r->nlanes);
     if (r->Lb / r->m >= (1ull << 27)) return fail(BBB_EINVAL, "nbits too large for one call (about 2^47): lower it");
-    BBB_HIP(hipMalloc((void **)&r->d_totals, 2 * (size_t)ncfg * sizeof(unsigned long long)));
-    if (hipMemset(r->d_totals, 0, 2 * (size_t)ncfg * sizeof(unsigned long long)) != hipSuccess) {
-        (void)hipFree(r->d_totals);            // (the unique_ptr frees the struct only)
+    const int rc = r->d_totals.grow(2 * (size_t)ncfg);
+    if (rc) return rc;
+    if (hipMemset(r->d_totals, 0, 2 * (size_t)ncfg * sizeof(unsigned long long)) != hipSuccess)
         return fail(BBB_EHIP, "hipMemset of the run's totals failed");
-    }
     *out = r.release();
     return BBB_OK;
 }
@@ -1945,25 +1922,21 @@ static int ber_run_step(bbb_ber_run *r, unsigned long long *counters_dev) {
         if ((rc = get_plan(h, r->Lb, &plan))) return rc;
         if ((rc = get_prbs_plan(h, c.prbs_k, r->Lb, &pp))) return rc;
         if ((rc = ensure_top_tables(plan))) return rc;
-        if ((rc = grow(&r->d_states, &r->states_cap, (size_t)65536 * h->W32))) return rc;
-        if ((rc = grow(&r->d_planes, &r->planes_cap, (size_t)h->k * r->nlanes))) return rc;
-        if ((rc = grow(&r->d_pplanes, &r->pplanes_cap, (size_t)32 * r->nlanes))) return rc;
-        uint64_t s0[8];
-        h->pw->apply(c.warmup + block_first + 1, h->init, s0);
+        if ((rc = r->d_states.grow((size_t)65536 * h->W32))) return rc;
+        if ((rc = r->d_planes.grow((size_t)h->k * r->nlanes))) return rc;
+        if ((rc = r->d_pplanes.grow((size_t)32 * r->nlanes))) return rc;
         uint32_t s16[256];
-        first16(*plan, s0, s16);
+        first16_at(h, *plan, c.warmup + block_first + 1, s16);
         uint64_t ps0 = 0;
         if ((rc = prbs_state_at_host(c.prbs_k, c.prbs_state, block_first, &ps0))) return rc;
         uint64_t ps64[8] = {ps0};
         uint32_t ps16[256];
         first16(*pp, ps64, ps16);
         { const int rcs_ = ensure_side_stream(h); if (rcs_) return rcs_; }
-        for (hipEvent_t *e : {&r->fork, &r->join})
-            if (!*e) BBB_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
-        BBB_HIP(hipEventRecord(r->fork, h->cs));                      // (the previous block's last kernel still reads the buffers)
+        if ((rc = r->fork.record(h->cs))) return rc;                 // (the previous block's last kernel still reads the buffers)
         BBB_HIP(hipStreamWaitEvent(h->side, r->fork, 0));
         if ((rc = prbs_seed_lanes_launch(c.prbs_k, pp->d_cols, ps16, pp->qcol64, r->G, r->nlanes, r->d_pplanes, h->side))) return rc;
-        BBB_HIP(hipEventRecord(r->join, h->side));
+        if ((rc = r->join.record(h->side))) return rc;
         if ((rc = awgn_seed_head_launch(h->k, plan->d_cols, s16, r->G, r->d_states, h->cs))) return rc;
         if ((rc = awgn_seed_tail_planes_launch(h->k, plan->d_top, r->G, r->d_states, r->nlanes, r->d_planes, h->cs))) return rc;
         BBB_HIP(hipStreamWaitEvent(h->cs, r->join, 0));
@@ -2022,11 +1995,7 @@ int bbb_ber_run_close(bbb_ber_run *r) {
     if (r->h && r->h->stream) (void)hipStreamSynchronize(r->h->stream);
     if (r->h && r->h->cs_valid) (void)hipStreamSynchronize(r->h->cs);
     if (r->h && r->h->side) (void)hipStreamSynchronize(r->h->side);
-    for (void *p : {(void *)r->d_states, (void *)r->d_planes, (void *)r->d_pstates, (void *)r->d_pplanes, (void *)r->d_totals})
-        if (p) (void)hipFree(p);
-    for (hipEvent_t e : {r->fork, r->join})
-        if (e) (void)hipEventDestroy(e);
-    delete r;
+    delete r;                                        // (its members free the buffers and destroy the events)
     return BBB_OK;
 }
 
@@ -2189,7 +2158,7 @@ int bbb_ber_sweep_multi(bbb_lutopt *const *handles, int ndev, const bbb_trial_cf
         BBB_HIP(hipStreamSynchronize(handles[r]->stream));
     }
     std::vector<std::vector<unsigned long long>> host((size_t)ndev);
-    for (int r = 0; r < ndev; r++) host[(size_t)r].assign(handles[r]->h_counters, handles[r]->h_counters + nwords);
+    for (int r = 0; r < ndev; r++) host[(size_t)r].assign(handles[r]->h_counters.p, handles[r]->h_counters.p + nwords);
     if (rehearsal) {                  // the sum the collective would have left on every device
         for (int r = 1; r < ndev; r++)
             for (size_t i = 0; i < nwords; i++) host[0][i] += host[(size_t)r][i];
