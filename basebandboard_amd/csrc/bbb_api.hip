@@ -2174,3 +2174,10 @@ int bbb_ber_sweep_multi(bbb_lutopt *const *handles, int ndev, const bbb_trial_cf
 }
 
 }  // extern "C"
+
+// what eye_api.hip needs of a handle and of a transmitter configuration (fields read, nothing changed)
+namespace bbb {
+int lutopt_device(const bbb_lutopt *h) { return h->device; }
+hipStream_t lutopt_stream(const bbb_lutopt *h) { return h->stream; }
+int tx_cfg_check(const bbb_tx_cfg *cfg) { return tx_check(cfg); }
+}  // namespace bbb

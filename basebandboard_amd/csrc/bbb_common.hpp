@@ -61,4 +61,27 @@ int prbs_detector_stream_launch(int k, const uint64_t *src, uint64_t nbits, uint
 int lutopt_search_launch(int k, uint64_t seed, uint64_t first, uint64_t count, uint64_t *found, uint16_t *taps_out,
                          uint32_t *row_off_out, bbb_search_stats *stats, hipStream_t st);
 
+// eye_kernels.hip
+struct EyeLaunch {
+    uint32_t ncols, shift;
+    uint64_t col_origin;
+    int32_t threshold, strict;
+    const unsigned long long *bits;   // data bits bit0 .. bit0 + nbits - 1 (packed LSB first); nullptr: no bathtub
+    long long bit0;
+    unsigned long long nbits;
+    int pulser;                       // 1: the Pulser's bits ((m & 255) == 0), `bits` unused
+    int want_hist, want_tub;
+};
+// blocks the accumulate kernel runs with on the current device for launches of up to nsamples (or a negative BBB_E* code),
+// and the u32 words of scratch they need for ncols
+int eye_grid_blocks(uint64_t nsamples);
+inline uint64_t eye_scratch_words(int blocks, uint32_t ncols) { return (uint64_t)blocks * (256u * ncols + 8u); }
+int eye_accumulate_launch(const EyeLaunch &a, const int16_t *samples, uint64_t nsamples, uint64_t first_sample,
+                          uint32_t *scratch, int blocks, uint64_t *hist, uint64_t *bathtub, hipStream_t st);
+
+// bbb_api.hip: what the eye object needs of a handle (reads fields only) and the bbb_tx_cfg checks of bbb_tx_fill_i16
+int lutopt_device(const bbb_lutopt *h);
+hipStream_t lutopt_stream(const bbb_lutopt *h);
+int tx_cfg_check(const bbb_tx_cfg *cfg);
+
 }  // namespace bbb

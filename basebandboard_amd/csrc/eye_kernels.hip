@@ -1,0 +1,234 @@
+// eye_kernels.hip -- eye histogram and bathtub counts of int16 samples (include/bbb.h, "eye diagram and bathtub").
+//
+// Reference semantics: the DSO of gateware/bbb/dso.py:12-72 (256 rows x 64 columns, row = 127 - sample, column = position
+// after a line trigger), counted instead of lit; the bathtub decides data bit m from sample 8m + 45 + p at phase p.
+//
+// One accumulate kernel serves the capture side (bbb_eye_accumulate_i16) and the transmitter side (bbb_tx_eye_run):
+//  - every block keeps its histogram in LDS as u32 counts laid out [256 rows][64 LANE-COLUMNS]: lane-column lc holds the
+//    samples with (n - col_origin) mod 64 = lc and is folded to column lc mod ncols at the flush.  The bank of a b32 LDS
+//    access is (a/4) mod 32 in lane groups of 32 (MI355X_MICROARCH.md, LDS), and row * 64 is a multiple of 32, so an
+//    instruction whose 32 lanes touch 32 distinct lane-columns mod 32 is free of conflicts whatever the rows are;
+//  - a thread reads 8 consecutive samples with one 16-byte load (group g of the body, g = lane mod 8 within 8 lanes), so at
+//    step j lanes l, l+4, ..., l+28 would all sit on lane-column cb + 8 (l mod 4) + j mod 32: eight lanes on one bank.  Each
+//    lane instead takes its 8 samples ROTATED by t = (l >> 2) & 7 (three select stages): at step j lane l adds sample
+//    (j + t) mod 8, and the 32 lanes of a group cover 32 distinct banks;
+//  - the flush writes the block's folded partial with plain stores to a scratch slab ([blocks][256 ncols + 8] u32); a small
+//    reduce kernel adds the slab into the u64 outputs (no global atomics: 256 blocks x 16 Ki bins would be 4 M of them);
+//  - bathtub errors are counted in registers per sample slot j (slot j of every group has the same phase), reduced per wave,
+//    then per block in LDS; the number of bits decided per phase is exact arithmetic on the range, added by the host.
+// Samples per launch are below 2^31 (the host cuts longer ranges), so every u32 count of a block is exact.
+#include "bbb_common.hpp"
+
+#include <algorithm>
+
+namespace bbb {
+
+constexpr int kEyeThreads = 1024;
+constexpr int kEyeRows = 256, kEyeLanes = 64;
+constexpr int kEyeUnroll = 4;                          // 16-byte loads in flight per thread
+constexpr uint64_t kEyeLaunchMax = 1ull << 31;         // samples per launch
+typedef uint32_t eye_u32x4 __attribute__((ext_vector_type(4)));
+
+struct EyeTubBits { unsigned long long v[8]; };
+
+__device__ __forceinline__ unsigned eye_row(int x, unsigned shift) {
+    int v = x >> shift;
+    v = v < -128 ? -128 : (v > 127 ? 127 : v);
+    return (unsigned)(127 - v);
+}
+
+__device__ __forceinline__ unsigned eye_decide(int x, int thr, int strict) { return strict ? (x > thr) : (x >= thr); }
+
+// data bit m, or -1 when it does not count (m < 0, or outside the bits supplied)
+__device__ __forceinline__ int eye_bit(const EyeLaunch &a, long long m) {
+    if (m < 0) return -1;
+    if (a.pulser) return (m & 255) == 0;                            // Pulser: counter == 0 (tx.py:28-30)
+    if (m < a.bit0) return -1;
+    const unsigned long long rel = (unsigned long long)(m - a.bit0);
+    if (rel >= a.nbits) return -1;
+    return (int)((a.bits[rel >> 6] >> (rel & 63)) & 1ull);
+}
+
+// samples [0, head) and [head + 8 ngroups, nsamples) of the launch are the "extras" (at most 7 + 7): the body's 16-byte loads
+// need x + head to be 16-byte aligned.
+template <bool HIST, bool TUB>
+__global__ void __launch_bounds__(kEyeThreads)
+eye_accumulate_kernel(EyeLaunch a, const int16_t *__restrict x, unsigned head, unsigned long long ngroups, unsigned long long nsamples,
+                      unsigned long long first, uint32_t *__restrict scratch) {
+    __shared__ uint32_t H[HIST ? kEyeRows * kEyeLanes : 1];
+    __shared__ uint32_t E[8];
+    if constexpr (HIST) {
+        eye_u32x4 *h4 = reinterpret_cast<eye_u32x4 *>(H);
+        for (int i = threadIdx.x; i < kEyeRows * kEyeLanes / 4; i += kEyeThreads) h4[i] = eye_u32x4{0u, 0u, 0u, 0u};
+    }
+    if (threadIdx.x < 8) E[threadIdx.x] = 0;
+    __syncthreads();
+
+    const unsigned lane = threadIdx.x & 63;
+    const unsigned rot = (lane >> 2) & 7;
+    const unsigned long long s0 = first + head;                              // sample number of the body's first sample
+    const unsigned cb = (unsigned)((s0 - a.col_origin) & 63) + 8u * (lane & 7);   // lane-column of this lane's slot 0 (g = lane mod 8)
+    const long long r0 = (long long)s0 - BBB_TX_BIT_SAMPLE0;
+    const long long F = r0 >> 3;                                             // floor: bit of slot 0 of group 0
+    const unsigned d = (unsigned)(r0 & 7);                                   // its phase; slots j >= 8 - d belong to bit F + g + 1
+    uint32_t err[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+
+    const eye_u32x4 *xv = reinterpret_cast<const eye_u32x4 *>(x + head);
+    const unsigned long long stride = (unsigned long long)gridDim.x * kEyeThreads;
+    for (unsigned long long g0 = (unsigned long long)blockIdx.x * kEyeThreads + threadIdx.x; g0 < ngroups; g0 += stride * kEyeUnroll) {
+        eye_u32x4 v[kEyeUnroll];
+#pragma unroll
+        for (int u = 0; u < kEyeUnroll; u++) {
+            const unsigned long long g = g0 + u * stride;
+            if (g < ngroups) v[u] = xv[g];
+        }
+#pragma unroll
+        for (int u = 0; u < kEyeUnroll; u++) {
+            const unsigned long long g = g0 + u * stride;
+            if (g >= ngroups) break;
+            int s[8];
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                s[2 * i] = (int)(int16_t)(v[u][i] & 0xffffu);
+                s[2 * i + 1] = (int)v[u][i] >> 16;
+            }
+            if constexpr (TUB) {
+                const long long m = F + (long long)g;
+                const int b0 = eye_bit(a, m), b1 = eye_bit(a, m + 1);
+#pragma unroll
+                for (int j = 0; j < 8; j++) {
+                    const int b = (unsigned)j < 8u - d ? b0 : b1;
+                    err[j] += (b >= 0) & (eye_decide(s[j], a.threshold, a.strict) != (unsigned)b);
+                }
+            }
+            if constexpr (HIST) {
+                unsigned A[8];
+#pragma unroll
+                for (int r = 0; r < 8; r++) A[r] = eye_row(s[r], a.shift) * kEyeLanes + ((cb + r) & 63);
+#pragma unroll
+                for (unsigned sh = 1; sh < 8; sh <<= 1) {                    // A[j] <- A[(j + rot) mod 8]
+                    const bool on = rot & sh;
+                    unsigned B[8];
+#pragma unroll
+                    for (int j = 0; j < 8; j++) B[j] = on ? A[(j + sh) & 7] : A[j];
+#pragma unroll
+                    for (int j = 0; j < 8; j++) A[j] = B[j];
+                }
+#pragma unroll
+                for (int j = 0; j < 8; j++) atomicAdd(&H[A[j]], 1u);
+            }
+        }
+    }
+
+    // the extras, one sample per thread of block 0
+    if (blockIdx.x == 0 && threadIdx.x < 16) {
+        const unsigned long long tail0 = head + 8 * ngroups;
+        const unsigned t = threadIdx.x;
+        const unsigned long long i = t < head ? t : tail0 + (t - head);
+        if (i < nsamples) {
+            const unsigned long long n = first + i;
+            const int xs = x[i];
+            if constexpr (HIST) atomicAdd(&H[eye_row(xs, a.shift) * kEyeLanes + (unsigned)((n - a.col_origin) & 63)], 1u);
+            if constexpr (TUB) {
+                const long long rn = (long long)n - BBB_TX_BIT_SAMPLE0;
+                const int b = eye_bit(a, rn >> 3);
+                if (b >= 0 && eye_decide(xs, a.threshold, a.strict) != (unsigned)b) atomicAdd(&E[rn & 7], 1u);
+            }
+        }
+    }
+    if constexpr (TUB) {
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            uint32_t e = err[j];
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) e += __shfl_xor(e, o);
+            if (lane == 0 && e) atomicAdd(&E[(d + j) & 7], e);
+        }
+    }
+    __syncthreads();
+
+    // flush: fold the 64 lane-columns to ncols and store the block's partial
+    const unsigned nbins = kEyeRows * a.ncols;
+    uint32_t *out = scratch + (unsigned long long)blockIdx.x * (nbins + 8);
+    if constexpr (HIST) {
+        const unsigned lg = 31 - __builtin_clz(a.ncols), fold = kEyeLanes >> lg;
+        for (unsigned bin = threadIdx.x; bin < nbins; bin += kEyeThreads) {
+            const unsigned row = bin >> lg, col = bin & (a.ncols - 1);
+            uint32_t sum = 0;
+            for (unsigned k = 0; k < fold; k++) sum += H[row * kEyeLanes + col + (k << lg)];
+            out[bin] = sum;
+        }
+    }
+    if (TUB && threadIdx.x < 8) out[nbins + threadIdx.x] = E[threadIdx.x];
+}
+
+// outputs += the slab: thread t < nbins sums bin t over the blocks, t = nbins + p the errors of phase p
+__global__ void __launch_bounds__(256)
+eye_reduce_kernel(const uint32_t *__restrict scratch, unsigned blocks, unsigned nbins, unsigned long long *__restrict hist,
+                  unsigned long long *__restrict tub, EyeTubBits bits) {
+    const unsigned t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= nbins + 8) return;
+    const bool is_tub = t >= nbins;
+    if (is_tub ? !tub : !hist) return;
+    unsigned long long sum = 0;
+    for (unsigned b = 0; b < blocks; b++) sum += scratch[(unsigned long long)b * (nbins + 8) + t];
+    if (!is_tub) {
+        hist[t] += sum;
+    } else {
+        const unsigned p = t - nbins;
+        tub[2 * p] += bits.v[p];
+        tub[2 * p + 1] += sum;
+    }
+}
+
+// the bits a range of samples decides at each phase: m >= 0 with 8m + 45 + p in [first, first + n)
+static void eye_tub_bits(uint64_t first, uint64_t n, EyeTubBits *b) {
+    const uint64_t last = first + n - 1;
+    for (int p = 0; p < 8; p++) {
+        const uint64_t s = BBB_TX_BIT_SAMPLE0 + p;
+        b->v[p] = 0;
+        if (last < s) continue;
+        const uint64_t lo = first <= s ? 0 : (first - s + 7) / 8, hi = (last - s) / 8;
+        b->v[p] = hi >= lo ? hi - lo + 1 : 0;
+    }
+}
+
+int eye_grid_blocks(uint64_t nsamples) {
+    int dev = 0, cus = 0;
+    BBB_HIP(hipGetDevice(&dev));
+    BBB_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    const uint64_t per_launch = std::min<uint64_t>(nsamples, kEyeLaunchMax);
+    // one block per CU (64 KiB of LDS, 16 waves); fewer for short launches: at least 16 groups of 8 samples per thread
+    const uint64_t want = (per_launch + (uint64_t)kEyeThreads * 128 - 1) / ((uint64_t)kEyeThreads * 128);
+    return (int)std::max<uint64_t>(1, std::min<uint64_t>(want, (uint64_t)std::max(cus, 1)));
+}
+
+int eye_accumulate_launch(const EyeLaunch &a, const int16_t *samples, uint64_t nsamples, uint64_t first_sample, uint32_t *scratch,
+                          int blocks, uint64_t *hist, uint64_t *bathtub, hipStream_t st) {
+    const unsigned nbins = kEyeRows * a.ncols;
+    for (uint64_t off = 0; off < nsamples;) {
+        const uint64_t n = std::min(nsamples - off, kEyeLaunchMax);
+        const int16_t *x = samples + off;
+        const unsigned head = (unsigned)std::min<uint64_t>(((16 - ((uintptr_t)x & 15)) & 15) / 2, n);
+        const uint64_t ngroups = (n - head) / 8;
+        const uint64_t want = (ngroups + kEyeThreads - 1) / kEyeThreads;
+        const unsigned nb = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)blocks, want));
+        const uint64_t first = first_sample + off;
+        if (a.want_hist && a.want_tub)
+            eye_accumulate_kernel<true, true><<<nb, kEyeThreads, 0, st>>>(a, x, head, ngroups, n, first, scratch);
+        else if (a.want_hist)
+            eye_accumulate_kernel<true, false><<<nb, kEyeThreads, 0, st>>>(a, x, head, ngroups, n, first, scratch);
+        else
+            eye_accumulate_kernel<false, true><<<nb, kEyeThreads, 0, st>>>(a, x, head, ngroups, n, first, scratch);
+        BBB_HIP(hipGetLastError());
+        EyeTubBits tb;
+        eye_tub_bits(first, n, &tb);
+        eye_reduce_kernel<<<(nbins + 8 + 255) / 256, 256, 0, st>>>(scratch, nb, nbins, reinterpret_cast<unsigned long long *>(a.want_hist ? hist : nullptr),
+                                                                   reinterpret_cast<unsigned long long *>(a.want_tub ? bathtub : nullptr), tb);
+        BBB_HIP(hipGetLastError());
+        off += n;
+    }
+    return BBB_OK;
+}
+
+}  // namespace bbb

@@ -69,6 +69,12 @@ class RX:
         bits, nbits = self.slice(samples, first_sample, stride)
         return self.prbsdet.run_stream(bits, nbits, want_err=want_err, want_reload=want_reload)
 
+    def eye(self, samples, first_sample=0, eye=None, hist=None):
+        """Eye histogram of an int16 CUDA tensor (bbb_eye_accumulate_i16): samples[i] is sample number first_sample + i;
+        `eye` an eye.EyeConfig (default 64 columns, shift 4).  Returns hist [256, ncols] uint64 (added to when given)."""
+        from .eye import capture_eye
+        return capture_eye(samples, first_sample, eye, hist)
+
     def phase_search(self, samples, stride=None, strict=False):
         """Every setting of the reference's `sample_delay` knob (0 .. samples_per_bit - 1; rx.py:19): the
         detector's totals per phase and the phase with the fewest errors."""

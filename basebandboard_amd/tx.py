@@ -50,6 +50,14 @@ class TX:
                        "bbb_awgn_prefetch")
         return out[:nsamples]
 
+    def eye(self, nsamples, first_sample=0, warmup=16, eye=None, chunk_samples=0, hist=None, bathtub=None):
+        """Eye histogram and bathtub of `x` over samples [first_sample, first_sample + nsamples), the waveform never
+        materialised (bbb_tx_eye_*): (hist [256, ncols] uint64, bathtub [8, 2] uint64 = bits, errors per phase).  `eye`: an
+        eye.EyeConfig, default 64 columns, shift 4 and col_origin = eye.BIT_SAMPLE0 (column c is bathtub phase c mod 8).
+        hist / bathtub given: added to."""
+        from .eye import tx_eye
+        return tx_eye(self, nsamples, first_sample, warmup, eye, chunk_samples, hist, bathtub)
+
     def stream(self, nsamples_per_call, first_sample=0, warmup=16):
         """TX.x read sequentially (bbb_tx_stream_*): `with tx.stream(n) as s: s.next(out=buf)`."""
         return WaveformStream(self, nsamples_per_call, first_sample, warmup)

@@ -8,6 +8,9 @@
 //                       --staged picks the level of bbb_lutopt_set_staged for it (default: the stream's own choice, two reads
 //                       per sample kernel; 0 = plain bbb_awgn_fill_i8 calls in the one-kernel form)
 //          loopback:    --loopback BITS
+//          eye:         --eye FILE [--eye-samples 1e6] [--prbs 31] [--nv 8] [--shape 16] [--shift 4]   eye diagram and bathtub of the
+//                       transmitter (bbb_tx_eye_*; raised-cosine set `shape` of tx.py:54, noise_var nv): the DSO's persistence
+//                       image (gateware/bbb/dso.py, 256 rows x 64 columns) written to FILE as a PGM, one line per bathtub phase
 //          search:      --search K [--seed S] [--count N] --out FILE    the reference's rnghunt (software/rnghunt/src/bin/
 //                       rnghunt.rs:13-66) on the GPU: candidates of `seed` are examined in windows of N (default 65536)
 //                       until one has period 2^K - 1; it is written to FILE in the reference's `out` format (K lines of K
@@ -53,6 +56,20 @@
     } while (0)
 
 static const double kHbmPeakGBs = 8000.0;     // MI355X HBM3E, nominal
+
+// The raised-cosine tap set of PRBSShaper.from_rcf (bitshaper.py:97-107; basebandboard_amd.bitshaper.rcf_coefficients): T = 8
+// samples per bit, peak 254, the two singular taps replaced by their limit, truncated towards zero.
+static double sinc(double x) { return x == 0.0 ? 1.0 : std::sin(M_PI * x) / (M_PI * x); }
+static void rcf_taps(double beta, int16_t *c) {
+    const double T = 8;
+    for (int i = 0; i < 64; i++) {
+        const double t = i - 32;
+        double v;
+        if (beta != 0.0 && std::fabs(t) == T / (2 * beta)) v = M_PI / (4 * T) * sinc(1 / (2 * beta));
+        else v = 1 / T * sinc(t / T) * std::cos(M_PI * beta * t / T) / (1 - (2 * beta * t / T) * (2 * beta * t / T));
+        c[i] = (int16_t)(long long)(v * T * 254);
+    }
+}
 
 static bool load_taps_file(const std::string &path, int *k, std::vector<uint16_t> *taps, std::vector<uint32_t> *off) {
     // packed tap lists: one row per line, space separated column indices (basebandboard_amd/data/*.taps)
@@ -141,6 +158,9 @@ int main(int argc, char **argv) {
     int k = 31, nv = 8, seeds = 1, gpus = 1, json = 0, steps = 5, multi = 0, staged = -1, search_k = 0;
     unsigned long long search_seed = 1, search_count = 65536;
     std::string outfile;
+    std::string eyefile;
+    int shape = 16, eye_shift = 4;
+    double eye_samples = 1e6;
     unsigned long long init0 = 1;
     double bits = 1e9, from = 0, to = 10, step = 1, loopback = 0, nsamples = 0;
     for (int i = 1; i + 1 < argc; i += 2) {
@@ -170,6 +190,10 @@ int main(int argc, char **argv) {
         else if (a == "--seed") search_seed = std::strtoull(v, nullptr, 0);
         else if (a == "--count") search_count = std::strtoull(v, nullptr, 0);
         else if (a == "--out") outfile = v;
+        else if (a == "--eye") eyefile = v;
+        else if (a == "--eye-samples") eye_samples = std::atof(v);
+        else if (a == "--shape") shape = std::atoi(v);
+        else if (a == "--shift") eye_shift = std::atoi(v);
         else if (a == "--gen") { if (std::string(v) != "lutopt") { std::fprintf(stderr, "--gen lutopt is the only generator the reference has\n"); return 2; } }
         else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
     }
@@ -242,6 +266,57 @@ int main(int argc, char **argv) {
         (void)bbb_lutopt_destroy(hh);
         return rc;
     };
+
+    // ---- eye diagram and bathtub of the transmitter (gateware/bbb/dso.py, drawn by ui.py) -------------------------------
+    if (!eyefile.empty()) {
+        if (shape < 0 || shape > 31 || eye_samples < 1) { std::fprintf(stderr, "--shape 0..31, --eye-samples >= 1\n"); return 2; }
+        bbb_tx_cfg cfg{};
+        rcf_taps(shape == 31 ? 1.0 : shape * (1.0 / 31), cfg.coeffs);          // tx.py:54: np.linspace(0, 1, 32)
+        cfg.source = 0;
+        cfg.prbs_k = k;
+        cfg.prbs_state = 1;
+        cfg.bit_en = 1;
+        cfg.noise_en = 1;
+        cfg.noise_var = nv;
+        cfg.warmup = 16;
+        const bbb_eye_cfg eye{64, (uint32_t)eye_shift, BBB_TX_BIT_SAMPLE0, 0, 0};
+        const uint64_t init[8] = {init0, 0, 0, 0, 0, 0, 0, 0};
+        bbb_lutopt *h = nullptr;
+        CHECK(bbb_lutopt_create(&h, m.n, m.taps.data(), m.off.data(), init, 0));
+        bbb_tx_eye *e = nullptr;
+        CHECK(bbb_tx_eye_open(h, &cfg, &eye, 0, &e));
+        const size_t nh = 256 * 64, nw = nh + 16;
+        uint64_t *d = nullptr;
+        if (hipMalloc((void **)&d, nw * sizeof(uint64_t)) != hipSuccess || hipMemset(d, 0, nw * sizeof(uint64_t)) != hipSuccess) {
+            std::fprintf(stderr, "hipMalloc failed\n");
+            return 1;
+        }
+        const double t0 = now_s();
+        CHECK(bbb_tx_eye_run(e, 0, (uint64_t)eye_samples, d, d + nh));
+        std::vector<uint64_t> out(nw);
+        if (hipMemcpy(out.data(), d, nw * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) { std::fprintf(stderr, "hipMemcpy failed\n"); return 1; }
+        const double secs = now_s() - t0;
+        CHECK(bbb_tx_eye_close(e));
+        CHECK(bbb_lutopt_destroy(h));
+        (void)hipFree(d);
+        FILE *f = std::fopen(eyefile.c_str(), "wb");
+        if (!f) { std::fprintf(stderr, "cannot write %s\n", eyefile.c_str()); return 1; }
+        std::fprintf(f, "P5\n64 256\n255\n");                               // the DSO's memory image: row << 6 | col
+        std::vector<unsigned char> img(nh);
+        for (size_t i = 0; i < nh; i++) img[i] = out[i] ? 255 : 0;
+        const bool ok = std::fwrite(img.data(), 1, nh, f) == nh;
+        if (std::fclose(f) != 0 || !ok) { std::fprintf(stderr, "cannot write %s\n", eyefile.c_str()); return 1; }
+        std::printf("{\"mode\": \"eye\", \"samples\": %llu, \"prbs\": %d, \"nv\": %d, \"shape\": %d, \"shift\": %d, \"seconds\": %.4f, "
+                    "\"pgm\": \"%s\", \"taps\": [", (unsigned long long)eye_samples, k, nv, shape, eye_shift, secs, eyefile.c_str());
+        for (int i = 0; i < 64; i++) std::printf("%s%d", i ? ", " : "", cfg.coeffs[i]);
+        std::printf("]}\n");
+        for (int p = 0; p < 8; p++) {
+            const uint64_t nb = out[nh + 2 * p], ne = out[nh + 2 * p + 1];
+            std::printf("{\"phase\": %d, \"bits\": %llu, \"errors\": %llu, \"ber\": %.6e}\n", p, (unsigned long long)nb,
+                        (unsigned long long)ne, nb ? (double)ne / (double)nb : 0.0);
+        }
+        return 0;
+    }
 
     // ---- AWGN fill mode (BASELINE configs[1]) -----------------------------------------------------------------------
     if (nsamples > 0) {

@@ -413,6 +413,47 @@ int bbb_rx_slice(const int16_t *samples_dev, uint64_t nsamples, uint64_t stride,
 int bbb_rx_phase_search(const int16_t *samples_dev, uint64_t nsamples, uint64_t stride, uint64_t nphases, int strict,
                         int k, bbb_detector_stats *stats_out, int device, void *hip_stream);
 
+/* ---- eye diagram and bathtub (gateware/bbb/dso.py, drawn by ui.py; software/memdump/eye.py) ---- */
+
+/* The DSO (dso.py:12-72) keeps 256 rows x 64 columns; a sample's row is 127 - sample (8-bit signed), its column is its
+ * position after a line trigger.  Here every sample is COUNTED:
+ *   row(x) = 127 - clamp(x >> shift, -128, 127)   (arithmetic shift; saturating where dso.py:68 truncates to 8 bits)
+ *   col(n) = (n - col_origin) mod ncols            (n = absolute sample number)
+ *   hist[row * ncols + col] += 1                   (uint64; for ncols = 64 the DSO address row << 6 | col, so hist > 0
+ *                                                   is the DSO's persistence image)
+ * Bathtub (transmitter side only).  The shaper formula above makes data bit m contribute coeffs[n - 17 - 8m] to sample n;
+ * tap 32 is the pulse centre (t = 0 of np.arange(-32, 32), bitshaper.py:99,123), so bit m peaks at n = 8m + 49.  Phase p
+ * (0..7) decides bit m from sample n = 8m + BBB_TX_BIT_SAMPLE0 + p (phase 4 is the pulse centre) with
+ *   decision = strict ? x > threshold : x >= threshold      (rx.py:29 at threshold 0; software/memdump/decode.py:15)
+ * bathtub[2p] += bits decided at phase p, bathtub[2p+1] += those whose decision differs from data bit m of the
+ * transmitter's source (PRBS-k from prbs_state, or the Pulser).  Only bits m >= 0 whose sample lies in the range count.
+ * Both outputs are ADDED TO (never overwritten), like bbb_ber_trials_dev: the totals do not depend on how a range is cut
+ * into calls, and a multi-GPU host reduces them with one collective. */
+#define BBB_TX_BIT_SAMPLE0 45
+typedef struct {
+    uint32_t ncols;       /* 8, 16, 32 or 64 columns (dso.py: 64) */
+    uint32_t shift;       /* 0..15: row = 127 - clamp(x >> shift, -128, 127) */
+    uint64_t col_origin;  /* sample n lands in column (n - col_origin) mod ncols */
+    int32_t  threshold;   /* bathtub decision: x >= threshold ... */
+    int32_t  strict;      /* ... or, with strict != 0, x > threshold */
+} bbb_eye_cfg;
+
+/* Capture side: the eye of any int16 samples already on the device (ADC captures, bbb_tx_fill_i16 output); samples_dev[i]
+ * is sample number first_sample + i.  hist_dev: [256][ncols] uint64, added to.  Any alignment of samples_dev (2 bytes).
+ * Asynchronous on hip_stream. */
+int bbb_eye_accumulate_i16(const int16_t *samples_dev, uint64_t nsamples, uint64_t first_sample, const bbb_eye_cfg *eye,
+                           uint64_t *hist_dev, int device, void *hip_stream);
+/* Transmitter side: eye and bathtub of TX.x (bbb_tx_fill_i16 of *cfg on the handle) over any sample range, the waveform never
+ * handed to the caller.  The object keeps copies of *cfg and *eye and owns its scratch: an int16 chunk of chunk_samples
+ * (0: 2^26, which fits the Infinity Cache), the chunk's data bits and the per-block partial histograms.  run covers samples
+ * [first_sample, first_sample + nsamples) chunk by chunk on the handle's stream (fill, data bits, accumulate), adding into
+ * hist_dev ([256][ncols] uint64) and bathtub_dev ([8][2] uint64); either may be NULL, not both.  Asynchronous.
+ * LIFETIME: as bbb_ber_run -- close the object BEFORE bbb_lutopt_destroy of its handle. */
+typedef struct bbb_tx_eye bbb_tx_eye;
+int bbb_tx_eye_open(bbb_lutopt *h, const bbb_tx_cfg *cfg, const bbb_eye_cfg *eye, uint64_t chunk_samples, bbb_tx_eye **out);
+int bbb_tx_eye_run(bbb_tx_eye *e, uint64_t first_sample, uint64_t nsamples, uint64_t *hist_dev, uint64_t *bathtub_dev);
+int bbb_tx_eye_close(bbb_tx_eye *e);
+
 /* ---- GF(2) helpers (host only; the pieces of software/rnghunt this path leans on) ------------ */
 
 /* Berlekamp-Massey (software/rnghunt/src/berlekamp_massey.rs:5-31): minimal polynomial of the bit
