@@ -79,6 +79,31 @@ inline uint64_t eye_scratch_words(int blocks, uint32_t ncols) { return (uint64_t
 int eye_accumulate_launch(const EyeLaunch &a, const int16_t *samples, uint64_t nsamples, uint64_t first_sample,
                           uint32_t *scratch, int blocks, uint64_t *hist, uint64_t *bathtub, hipStream_t st);
 
+// txsweep_kernels.hip: the BER sweep over transmitter settings (include/bbb.h, bbb_tx_ber_sweep_*)
+constexpr int kSweepMaxPairs = 8;                 // settings per launch: two per packed 16-bit lane operation
+struct SweepGroup {                               // one launch: settings sharing one shaped-value table
+    int table;                                    // index into the object's tables
+    int pairs;                                    // 1..kSweepMaxPairs
+    bool thr;                                     // some threshold of the group is not 0 after the strict shift
+    uint32_t nv2[kSweepMaxPairs], t0[kSweepMaxPairs], t1[kSweepMaxPairs];    // packed (low: setting 2k, high: 2k + 1)
+    int32_t idx[2 * kSweepMaxPairs];              // the settings' indices into the counters, -1 for padding
+};
+struct SweepChunk {                               // what a chunk hands every launch
+    const int8_t *noise;                          // noise of the chunk's samples, nullptr: no setting has noise on
+    const unsigned long long *bits;               // data bits m0 .. m0 + navail - 1; nullptr for the Pulser
+    long long m0;
+    unsigned long long navail;
+    int source;                                   // 0 PRBS, 1 Pulser
+    uint64_t first, n;                            // the chunk's samples [first, first + n), n <= 2^31
+};
+// the tables (8 x 256 u16 each) of ntab coefficient sets coeffs[ntab][64], built on the device once
+int sweep_tables_launch(const int16_t *coeffs_dev, int ntab, uint16_t *tables, hipStream_t st);
+// blocks a sweep launch runs with for up to n samples (or a negative BBB_E* code), and its scratch in u32 words
+int sweep_grid_blocks(uint64_t n);
+inline uint64_t sweep_scratch_words(int blocks) { return (uint64_t)blocks * (2 * kSweepMaxPairs * 8); }
+int sweep_launch(const SweepGroup &g, const uint16_t *tables, const SweepChunk &c, uint32_t *scratch, int blocks,
+                 uint64_t *counters, hipStream_t st);
+
 // bbb_api.hip: what the eye object needs of a handle (reads fields only) and the bbb_tx_cfg checks of bbb_tx_fill_i16
 int lutopt_device(const bbb_lutopt *h);
 hipStream_t lutopt_stream(const bbb_lutopt *h);

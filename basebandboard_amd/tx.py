@@ -58,6 +58,16 @@ class TX:
         from .eye import tx_eye
         return tx_eye(self, nsamples, first_sample, warmup, eye, chunk_samples, hist, bathtub)
 
+    def ber_sweep(self, nsamples, noise_vars=range(16), shape_sels=None, threshold=0, strict=False, first_sample=0, warmup=16,
+                  chunk_samples=0, counters=None):
+        """Bathtub of `x` for every (shape_sel, noise_var) of the grid in one pass over the noise stream
+        (bbb_tx_ber_sweep_*): [len(shape_sels), len(noise_vars), 8, 2] uint64 = bits, errors per phase, each entry what
+        TX.eye's bathtub gives for a TX with that shape_sel and noise_var.  shape_sels None: the TX's own set; bit_en and
+        noise_en are the TX's; the decision x >= threshold (x > threshold when strict).  counters given: added to."""
+        from .txsweep import tx_ber_sweep
+        return tx_ber_sweep(self, nsamples, noise_vars, shape_sels, threshold, strict, first_sample, warmup, chunk_samples,
+                            counters)
+
     def stream(self, nsamples_per_call, first_sample=0, warmup=16):
         """TX.x read sequentially (bbb_tx_stream_*): `with tx.stream(n) as s: s.next(out=buf)`."""
         return WaveformStream(self, nsamples_per_call, first_sample, warmup)

@@ -11,6 +11,9 @@
 //          eye:         --eye FILE [--eye-samples 1e6] [--prbs 31] [--nv 8] [--shape 16] [--shift 4]   eye diagram and bathtub of the
 //                       transmitter (bbb_tx_eye_*; raised-cosine set `shape` of tx.py:54, noise_var nv): the DSO's persistence
 //                       image (gateware/bbb/dso.py, 256 rows x 64 columns) written to FILE as a PGM, one line per bathtub phase
+//          tx sweep:    --tx-sweep 1 [--eye-samples 1e6] [--prbs 31] [--shape 16] [--nv-range 0:15]   BER of the shaped link for
+//                       every noise_var A..B of raised-cosine set `shape` in one pass (bbb_tx_ber_sweep_*): one JSON line per
+//                       setting and phase (bits decided, errors) after a header line
 //          search:      --search K [--seed S] [--count N] --out FILE    the reference's rnghunt (software/rnghunt/src/bin/
 //                       rnghunt.rs:13-66) on the GPU: candidates of `seed` are examined in windows of N (default 65536)
 //                       until one has period 2^K - 1; it is written to FILE in the reference's `out` format (K lines of K
@@ -161,6 +164,7 @@ int main(int argc, char **argv) {
     std::string eyefile;
     int shape = 16, eye_shift = 4;
     double eye_samples = 1e6;
+    int tx_sweep = 0, nv_lo = 0, nv_hi = 15;
     unsigned long long init0 = 1;
     double bits = 1e9, from = 0, to = 10, step = 1, loopback = 0, nsamples = 0;
     for (int i = 1; i + 1 < argc; i += 2) {
@@ -194,6 +198,10 @@ int main(int argc, char **argv) {
         else if (a == "--eye-samples") eye_samples = std::atof(v);
         else if (a == "--shape") shape = std::atoi(v);
         else if (a == "--shift") eye_shift = std::atoi(v);
+        else if (a == "--tx-sweep") tx_sweep = std::atoi(v);
+        else if (a == "--nv-range") {
+            if (std::sscanf(v, "%d:%d", &nv_lo, &nv_hi) != 2) { std::fprintf(stderr, "--nv-range A:B\n"); return 2; }
+        }
         else if (a == "--gen") { if (std::string(v) != "lutopt") { std::fprintf(stderr, "--gen lutopt is the only generator the reference has\n"); return 2; } }
         else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
     }
@@ -315,6 +323,57 @@ int main(int argc, char **argv) {
             std::printf("{\"phase\": %d, \"bits\": %llu, \"errors\": %llu, \"ber\": %.6e}\n", p, (unsigned long long)nb,
                         (unsigned long long)ne, nb ? (double)ne / (double)nb : 0.0);
         }
+        return 0;
+    }
+
+    // ---- BER of the shaped link over noise_var in one pass (bbb_tx_ber_sweep_*) ------------------------------------------
+    if (tx_sweep) {
+        if (shape < 0 || shape > 31 || eye_samples < 1 || nv_lo < 0 || nv_hi > 15 || nv_lo > nv_hi) {
+            std::fprintf(stderr, "--shape 0..31, --eye-samples >= 1, --nv-range A:B with 0 <= A <= B <= 15\n");
+            return 2;
+        }
+        bbb_tx_cfg base{};
+        base.source = 0;
+        base.prbs_k = k;
+        base.prbs_state = 1;
+        base.warmup = 16;
+        std::vector<bbb_tx_setting> settings;
+        for (int v = nv_lo; v <= nv_hi; v++) {
+            bbb_tx_setting st{};
+            rcf_taps(shape == 31 ? 1.0 : shape * (1.0 / 31), st.coeffs);        // tx.py:54: np.linspace(0, 1, 32)
+            st.bit_en = 1;
+            st.noise_en = 1;
+            st.noise_var = v;
+            settings.push_back(st);
+        }
+        const int nset = (int)settings.size();
+        const uint64_t init[8] = {init0, 0, 0, 0, 0, 0, 0, 0};
+        bbb_lutopt *h = nullptr;
+        CHECK(bbb_lutopt_create(&h, m.n, m.taps.data(), m.off.data(), init, 0));
+        bbb_tx_ber_sweep *s = nullptr;
+        CHECK(bbb_tx_ber_sweep_open(h, &base, settings.data(), nset, 0, &s));
+        const size_t nw = (size_t)nset * 16;
+        uint64_t *d = nullptr;
+        if (hipMalloc((void **)&d, nw * sizeof(uint64_t)) != hipSuccess || hipMemset(d, 0, nw * sizeof(uint64_t)) != hipSuccess) {
+            std::fprintf(stderr, "hipMalloc failed\n");
+            return 1;
+        }
+        const double t0 = now_s();
+        CHECK(bbb_tx_ber_sweep_run(s, 0, (uint64_t)eye_samples, d));
+        std::vector<uint64_t> out(nw);
+        if (hipMemcpy(out.data(), d, nw * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) { std::fprintf(stderr, "hipMemcpy failed\n"); return 1; }
+        const double secs = now_s() - t0;
+        CHECK(bbb_tx_ber_sweep_close(s));
+        CHECK(bbb_lutopt_destroy(h));
+        (void)hipFree(d);
+        std::printf("{\"mode\": \"tx-sweep\", \"samples\": %llu, \"prbs\": %d, \"shape\": %d, \"settings\": %d, \"seconds\": %.4f}\n",
+                    (unsigned long long)eye_samples, k, shape, nset, secs);
+        for (int i = 0; i < nset; i++)
+            for (int p = 0; p < 8; p++) {
+                const uint64_t nb = out[(size_t)i * 16 + 2 * p], ne = out[(size_t)i * 16 + 2 * p + 1];
+                std::printf("{\"shape\": %d, \"nv\": %d, \"phase\": %d, \"bits\": %llu, \"errors\": %llu, \"ber\": %.6e}\n", shape,
+                            nv_lo + i, p, (unsigned long long)nb, (unsigned long long)ne, nb ? (double)ne / (double)nb : 0.0);
+            }
         return 0;
     }
 

@@ -454,6 +454,31 @@ int bbb_tx_eye_open(bbb_lutopt *h, const bbb_tx_cfg *cfg, const bbb_eye_cfg *eye
 int bbb_tx_eye_run(bbb_tx_eye *e, uint64_t first_sample, uint64_t nsamples, uint64_t *hist_dev, uint64_t *bathtub_dev);
 int bbb_tx_eye_close(bbb_tx_eye *e);
 
+/* ---- BER of the shaped link over many transmitter settings in one pass --------------------------------------------- */
+
+/* One setting of the transmitter's knobs (tx.py:39-54: the shape set, bit_en, noise_en, noise_var) and of the receiver's
+ * decision (as bbb_eye_cfg).  coeffs each in (-256, 255]; noise_var 0..15; reserved must be 0. */
+typedef struct {
+    int16_t coeffs[64];          /* one coefficient set, as bbb_tx_cfg */
+    int32_t bit_en, noise_en, noise_var;
+    int32_t threshold, strict;   /* decision, as bbb_eye_cfg */
+    int32_t reserved;            /* must be 0 */
+} bbb_tx_setting;
+/* The bathtub of bbb_tx_eye_run for nset settings at once.  counters_dev is [nset][8][2] uint64 and is ADDED TO: entry
+ * [i][p] receives exactly what bathtub_dev[p] of bbb_tx_eye_run receives for the bbb_tx_cfg equal to *base with coeffs,
+ * bit_en, noise_en and noise_var taken from settings[i], and an eye cfg with settings[i]'s threshold / strict, over the same
+ * range.  *base supplies source, prbs_k, prbs_state and warmup; its other fields are ignored.  nset is 1..512 (the 32 x 16
+ * shape x noise_var grid of the board fits one object).  The noise sample and the data bits of a sample are the same for
+ * every setting, so run generates them once per chunk (chunk_samples, 0: 2^26 int8 samples, which stay in the Infinity
+ * Cache) and every group of settings re-reads them from there: the noise stream is generated once, whatever nset is.
+ * Handles that bbb_tx_fill_i16 refuses with noise on get the same BBB_EUNSUP from run when a setting has noise_en.
+ * Asynchronous on the handle's stream.  LIFETIME: as bbb_tx_eye -- close the object BEFORE bbb_lutopt_destroy of its handle. */
+typedef struct bbb_tx_ber_sweep bbb_tx_ber_sweep;
+int bbb_tx_ber_sweep_open(bbb_lutopt *h, const bbb_tx_cfg *base, const bbb_tx_setting *settings, int nset,
+                          uint64_t chunk_samples, bbb_tx_ber_sweep **out);
+int bbb_tx_ber_sweep_run(bbb_tx_ber_sweep *s, uint64_t first_sample, uint64_t nsamples, uint64_t *counters_dev);
+int bbb_tx_ber_sweep_close(bbb_tx_ber_sweep *s);
+
 /* ---- GF(2) helpers (host only; the pieces of software/rnghunt this path leans on) ------------ */
 
 /* Berlekamp-Massey (software/rnghunt/src/berlekamp_massey.rs:5-31): minimal polynomial of the bit
