@@ -104,6 +104,17 @@ inline uint64_t sweep_scratch_words(int blocks) { return (uint64_t)blocks * (2 *
 int sweep_launch(const SweepGroup &g, const uint16_t *tables, const SweepChunk &c, uint32_t *scratch, int blocks,
                  uint64_t *counters, hipStream_t st);
 
+// acf_kernels.hip: the autocorrelation counters (include/bbb.h, bbb_acf_accumulate_i16 / bbb_tx_acf_*)
+struct AcfPlan {
+    int gx, gy;                                   // workgroups over the stages (gx < 0: the device could not be queried)
+    size_t smem;                                  // dynamic LDS per workgroup
+    uint64_t partial_words, scratch_words;        // u64 words of the partials slab; of all scratch (slab, count, list)
+};
+// the grid of launches of up to max_nfirst first elements at nlags on the current device
+AcfPlan acf_plan(uint32_t nlags, uint64_t max_nfirst);
+int acf_launch(const AcfPlan &p, const int16_t *samples, uint64_t nfirst, uint64_t navail, uint32_t nlags, uint64_t *scratch,
+               uint64_t *acf, hipStream_t st);
+
 // bbb_api.hip: what the eye object needs of a handle (reads fields only) and the bbb_tx_cfg checks of bbb_tx_fill_i16
 int lutopt_device(const bbb_lutopt *h);
 hipStream_t lutopt_stream(const bbb_lutopt *h);

@@ -75,6 +75,21 @@ class RX:
         from .eye import capture_eye
         return capture_eye(samples, first_sample, eye, hist)
 
+    def acf(self, samples, nlags=256, nfirst=None, acf=None):
+        """Autocorrelation counters of an int16 CUDA tensor (bbb_acf_accumulate_i16): [nlags + 1] int64, acf[l] = sum over
+        first elements n < nfirst (default: all) of x[n] x[n + l] (0 beyond the tensor), acf[nlags] = their sum.  Added
+        to when given."""
+        from .spectrum import capture_acf
+        return capture_acf(samples, nlags, nfirst, acf)
+
+    def spectrum(self, samples, nlags=256, nfirst=None, **psd_kw):
+        """(freqs, psd) of an int16 CUDA tensor: spectrum.psd of RX.acf (Bartlett lag window by default: the averaged
+        periodogram of nlags-sample segments, software/memdump/fftplot.py's view).  psd_kw: window, nfft, fs, detrend,
+        onesided."""
+        from .spectrum import capture_acf, psd
+        n = samples.numel() if nfirst is None else int(nfirst)
+        return psd(capture_acf(samples, nlags, nfirst), n, **psd_kw)
+
     def phase_search(self, samples, stride=None, strict=False):
         """Every setting of the reference's `sample_delay` knob (0 .. samples_per_bit - 1; rx.py:19): the
         detector's totals per phase and the phase with the fewest errors."""

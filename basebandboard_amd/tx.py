@@ -58,6 +58,21 @@ class TX:
         from .eye import tx_eye
         return tx_eye(self, nsamples, first_sample, warmup, eye, chunk_samples, hist, bathtub)
 
+    def acf(self, nsamples, first_sample=0, nlags=256, warmup=16, chunk_samples=0, acf=None):
+        """Autocorrelation counters of `x` (bbb_tx_acf_*), the waveform never materialised: [nlags + 1] int64, acf[l] = sum
+        of x[n] x[n + l] over first elements n in [first_sample, first_sample + nsamples), acf[nlags] = sum of those x[n].
+        Added to when given."""
+        from .spectrum import tx_acf
+        return tx_acf(self, nsamples, first_sample, nlags, warmup, chunk_samples, acf)
+
+    def spectrum(self, nsamples, first_sample=0, nlags=256, warmup=16, chunk_samples=0, **psd_kw):
+        """(freqs, psd) of `x` over nsamples first elements: spectrum.psd of TX.acf (Bartlett lag window by default: what
+        the spectrum analyser shows with averaging).  The noise generator's own spectrum is that of
+        TX(k, bit_en=0, src_sel=0, shape_sel, noise_en=1, noise_var=1): the waveform is then wrap12(g * 1) = g.
+        psd_kw: window, nfft, fs, detrend, onesided."""
+        from .spectrum import psd, tx_acf
+        return psd(tx_acf(self, nsamples, first_sample, nlags, warmup, chunk_samples), int(nsamples), **psd_kw)
+
     def ber_sweep(self, nsamples, noise_vars=range(16), shape_sels=None, threshold=0, strict=False, first_sample=0, warmup=16,
                   chunk_samples=0, counters=None):
         """Bathtub of `x` for every (shape_sel, noise_var) of the grid in one pass over the noise stream

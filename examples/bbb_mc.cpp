@@ -14,6 +14,10 @@
 //          tx sweep:    --tx-sweep 1 [--eye-samples 1e6] [--prbs 31] [--shape 16] [--nv-range 0:15]   BER of the shaped link for
 //                       every noise_var A..B of raised-cosine set `shape` in one pass (bbb_tx_ber_sweep_*): one JSON line per
 //                       setting and phase (bits decided, errors) after a header line
+//          spectrum:    --spectrum FILE [--lags 256] [--eye-samples 1e6] [--prbs 31] [--nv 8] [--shape 16]   autocorrelation
+//                       counters of the transmitter's waveform (bbb_tx_acf_*) and the power spectrum from them (Bartlett lag
+//                       window, mean removed, one-sided, fs = 1): FILE gets a CSV k,freq,psd,psd_db (psd_db is nan in a bin
+//                       where the finite-record estimate dips below zero); one JSON line with the counters
 //          search:      --search K [--seed S] [--count N] --out FILE    the reference's rnghunt (software/rnghunt/src/bin/
 //                       rnghunt.rs:13-66) on the GPU: candidates of `seed` are examined in windows of N (default 65536)
 //                       until one has period 2^K - 1; it is written to FILE in the reference's `out` format (K lines of K
@@ -161,7 +165,8 @@ int main(int argc, char **argv) {
     int k = 31, nv = 8, seeds = 1, gpus = 1, json = 0, steps = 5, multi = 0, staged = -1, search_k = 0;
     unsigned long long search_seed = 1, search_count = 65536;
     std::string outfile;
-    std::string eyefile;
+    std::string eyefile, specfile;
+    int lags = 256;
     int shape = 16, eye_shift = 4;
     double eye_samples = 1e6;
     int tx_sweep = 0, nv_lo = 0, nv_hi = 15;
@@ -195,6 +200,8 @@ int main(int argc, char **argv) {
         else if (a == "--count") search_count = std::strtoull(v, nullptr, 0);
         else if (a == "--out") outfile = v;
         else if (a == "--eye") eyefile = v;
+        else if (a == "--spectrum") specfile = v;
+        else if (a == "--lags") lags = std::atoi(v);
         else if (a == "--eye-samples") eye_samples = std::atof(v);
         else if (a == "--shape") shape = std::atoi(v);
         else if (a == "--shift") eye_shift = std::atoi(v);
@@ -323,6 +330,70 @@ int main(int argc, char **argv) {
             std::printf("{\"phase\": %d, \"bits\": %llu, \"errors\": %llu, \"ber\": %.6e}\n", p, (unsigned long long)nb,
                         (unsigned long long)ne, nb ? (double)ne / (double)nb : 0.0);
         }
+        return 0;
+    }
+
+    // ---- autocorrelation and power spectrum of the transmitter (software/memdump/fftplot.py) -----------------------------
+    if (!specfile.empty()) {
+        if (shape < 0 || shape > 31 || eye_samples < 1 || lags < 1 || lags > BBB_ACF_MAX_LAGS) {
+            std::fprintf(stderr, "--shape 0..31, --eye-samples >= 1, --lags 1..%d\n", BBB_ACF_MAX_LAGS);
+            return 2;
+        }
+        bbb_tx_cfg cfg{};
+        rcf_taps(shape == 31 ? 1.0 : shape * (1.0 / 31), cfg.coeffs);          // tx.py:54: np.linspace(0, 1, 32)
+        cfg.source = 0;
+        cfg.prbs_k = k;
+        cfg.prbs_state = 1;
+        cfg.bit_en = 1;
+        cfg.noise_en = 1;
+        cfg.noise_var = nv;
+        cfg.warmup = 16;
+        const uint64_t init[8] = {init0, 0, 0, 0, 0, 0, 0, 0};
+        bbb_lutopt *h = nullptr;
+        CHECK(bbb_lutopt_create(&h, m.n, m.taps.data(), m.off.data(), init, 0));
+        bbb_tx_acf *a = nullptr;
+        CHECK(bbb_tx_acf_open(h, &cfg, (uint32_t)lags, 0, &a));
+        const size_t nw = (size_t)lags + 1;
+        int64_t *d = nullptr;
+        if (hipMalloc((void **)&d, nw * sizeof(int64_t)) != hipSuccess || hipMemset(d, 0, nw * sizeof(int64_t)) != hipSuccess) {
+            std::fprintf(stderr, "hipMalloc failed\n");
+            return 1;
+        }
+        const uint64_t count = (uint64_t)eye_samples;
+        const double t0 = now_s();
+        CHECK(bbb_tx_acf_run(a, 0, count, d));
+        std::vector<int64_t> acf(nw);
+        if (hipMemcpy(acf.data(), d, nw * sizeof(int64_t), hipMemcpyDeviceToHost) != hipSuccess) { std::fprintf(stderr, "hipMemcpy failed\n"); return 1; }
+        const double secs = now_s() - t0;
+        CHECK(bbb_tx_acf_close(a));
+        CHECK(bbb_lutopt_destroy(h));
+        (void)hipFree(d);
+        // Blackman-Tukey: c[l] = acf[l] / count - mu^2, Bartlett window w[l] = 1 - l / L, P[k] = w[0] c[0] + 2 sum_l w[l] c[l]
+        // cos(2 pi k l / nfft) over nfft = the smallest power of two >= 2L, bins 1 .. nfft/2 - 1 doubled (one-sided)
+        const int L = lags;
+        uint64_t nfft = 2;
+        while (nfft < 2 * (uint64_t)L) nfft *= 2;
+        const double mu = (double)acf[L] / (double)count;
+        std::vector<double> y(L), table(nfft);
+        for (int l = 0; l < L; l++) y[l] = (1.0 - (double)l / L) * ((double)acf[l] / (double)count - mu * mu);
+        for (uint64_t j = 0; j < nfft; j++) table[j] = std::cos(2 * M_PI * (double)j / (double)nfft);
+        FILE *f = std::fopen(specfile.c_str(), "w");
+        if (!f) { std::fprintf(stderr, "cannot write %s\n", specfile.c_str()); return 1; }
+        bool ok = std::fprintf(f, "k,freq,psd,psd_db\n") > 0;
+        for (uint64_t kb = 0; kb <= nfft / 2; kb++) {
+            double s = 0;
+            for (int l = 1; l < L; l++) s += y[l] * table[(kb * (uint64_t)l) % nfft];
+            double p = y[0] + 2 * s;
+            if (kb > 0 && kb < nfft / 2) p *= 2;
+            ok = ok && std::fprintf(f, "%llu,%.17g,%.17g,%.17g\n", (unsigned long long)kb, (double)kb / (double)nfft, p,
+                                    10 * std::log10(p)) > 0;
+        }
+        if (std::fclose(f) != 0 || !ok) { std::fprintf(stderr, "cannot write %s\n", specfile.c_str()); return 1; }
+        std::printf("{\"mode\": \"spectrum\", \"samples\": %llu, \"prbs\": %d, \"nv\": %d, \"shape\": %d, \"lags\": %d, \"nfft\": %llu, "
+                    "\"seconds\": %.4f, \"csv\": \"%s\", \"acf\": [", (unsigned long long)count, k, nv, shape, L,
+                    (unsigned long long)nfft, secs, specfile.c_str());
+        for (size_t i = 0; i < nw; i++) std::printf("%s%lld", i ? ", " : "", (long long)acf[i]);
+        std::printf("]}\n");
         return 0;
     }
 

@@ -479,6 +479,33 @@ int bbb_tx_ber_sweep_open(bbb_lutopt *h, const bbb_tx_cfg *base, const bbb_tx_se
 int bbb_tx_ber_sweep_run(bbb_tx_ber_sweep *s, uint64_t first_sample, uint64_t nsamples, uint64_t *counters_dev);
 int bbb_tx_ber_sweep_close(bbb_tx_ber_sweep *s);
 
+/* ---- autocorrelation counters: the waveform in frequency (software/memdump/fftplot.py) ------------------------------ */
+
+/* Exact integer counters from which a host computes the power spectrum (a Blackman-Tukey estimate: with a Bartlett lag
+ * window it is the expected averaged periodogram of nlags-sample segments, what a spectrum analyser shows with averaging).
+ * Capture side: for l in [0, nlags)
+ *   acf_dev[l]     += sum_{i < nfirst} x[i] * x[i + l]     with x[j] = samples_dev[j] for j < navail, 0 beyond
+ *   acf_dev[nlags] += sum_{i < nfirst} x[i]
+ * int64, added to modulo 2^64.  Exact while the true sums fit int64: more than 2^41 first elements for |x| <= 2048,
+ * more than 2^32 for full-range int16.  navail >= nfirst.  navail = nfirst is the biased estimate of one whole capture;
+ * navail = nfirst + nlags - 1 lets consecutive slices of one long record add up to the record's counters exactly.
+ * nlags 1..BBB_ACF_MAX_LAGS; nfirst = 0 is a no-op.  Any 2-byte alignment.  Asynchronous on hip_stream.
+ * MEMORY: a call's scratch (8 bytes per 4096 first elements for every started 320 lags, plus a few MiB of partials) comes
+ * from a memory pool the library creates per device and never releases: what the largest call took stays reserved for the
+ * rest of the process, outside any other allocator's view, and is reused by later calls. */
+#define BBB_ACF_MAX_LAGS 4096
+int bbb_acf_accumulate_i16(const int16_t *samples_dev, uint64_t nfirst, uint64_t navail, uint32_t nlags,
+                           int64_t *acf_dev, int device, void *hip_stream);
+/* Transmitter side: the same counters over TX.x (bbb_tx_fill_i16 of *cfg on the handle), first elements
+ * [first_sample, first_sample + nsamples).  The partners always exist, because the waveform continues.  The object keeps a
+ * copy of *cfg and owns an int16 chunk of chunk_samples + nlags - 1 samples (chunk_samples 0: 2^26) and the partials;
+ * run fills and correlates chunk by chunk on the handle's stream.  nsamples = 0 is a no-op.  Asynchronous.
+ * LIFETIME: as bbb_tx_eye -- close the object BEFORE bbb_lutopt_destroy of its handle. */
+typedef struct bbb_tx_acf bbb_tx_acf;
+int bbb_tx_acf_open(bbb_lutopt *h, const bbb_tx_cfg *cfg, uint32_t nlags, uint64_t chunk_samples, bbb_tx_acf **out);
+int bbb_tx_acf_run(bbb_tx_acf *a, uint64_t first_sample, uint64_t nsamples, int64_t *acf_dev);
+int bbb_tx_acf_close(bbb_tx_acf *a);
+
 /* ---- GF(2) helpers (host only; the pieces of software/rnghunt this path leans on) ------------ */
 
 /* Berlekamp-Massey (software/rnghunt/src/berlekamp_massey.rs:5-31): minimal polynomial of the bit
