@@ -115,6 +115,28 @@ AcfPlan acf_plan(uint32_t nlags, uint64_t max_nfirst);
 int acf_launch(const AcfPlan &p, const int16_t *samples, uint64_t nfirst, uint64_t navail, uint32_t nlags, uint64_t *scratch,
                uint64_t *acf, hipStream_t st);
 
+// nco_kernels.hip: the numerically controlled oscillator (include/bbb.h, bbb_nco_*)
+constexpr int kNcoThreads = 512;                  // threads per workgroup
+constexpr int kNcoReps = 16;                      // replicas of the ROM in LDS (lane l reads replica l % 16)
+constexpr int kNcoScanSteps = 4;                  // workgroup steps of 4096 samples per tile of the fm scan
+struct NcoLaunch {                                // one launch: up to 2^31 samples from the state in *in
+    const int32_t *fm;                            // per-sample buffers (nullptr: the constant below)
+    const uint16_t *am;
+    const int16_t *pm;
+    int16_t *x;
+    uint64_t n;
+    uint32_t fcw, am_c;
+    int32_t fm_c, pm_c;
+    int vec;                                      // every buffer given is 16-byte aligned: 16-byte loads and stores
+    const int16_t *rom;                           // the 1024 ROM entries on the device
+    const bbb_nco_state *in;                      // the state before the launch ...
+    bbb_nco_state *out;                           // ... and after it (another slot)
+    uint32_t *tiles;                              // fm scan: nco_tiles(n) tile sums, then offsets
+};
+uint64_t nco_tiles(uint64_t n);
+int nco_launch(const NcoLaunch &a, int grid, hipStream_t st);
+int nco_put_state(const bbb_nco_state &s, bbb_nco_state *dst, hipStream_t st);   // one thread, a plain store
+
 // bbb_api.hip: what the eye object needs of a handle (reads fields only) and the bbb_tx_cfg checks of bbb_tx_fill_i16
 int lutopt_device(const bbb_lutopt *h);
 hipStream_t lutopt_stream(const bbb_lutopt *h);

@@ -14,6 +14,8 @@
 //          tx sweep:    --tx-sweep 1 [--eye-samples 1e6] [--prbs 31] [--shape 16] [--nv-range 0:15]   BER of the shaped link for
 //                       every noise_var A..B of raised-cosine set `shape` in one pass (bbb_tx_ber_sweep_*): one JSON line per
 //                       setting and phase (bits decided, errors) after a header line
+//          nco:         --nco FILE [--fcw 1048576] [--am 16384] [--nco-samples 1e6]   the NCO's tone (bbb_nco_*), written as
+//                       little-endian int16 samples (software/memdump's `<h` format)
 //          spectrum:    --spectrum FILE [--lags 256] [--eye-samples 1e6] [--prbs 31] [--nv 8] [--shape 16]   autocorrelation
 //                       counters of the transmitter's waveform (bbb_tx_acf_*) and the power spectrum from them (Bartlett lag
 //                       window, mean removed, one-sided, fs = 1): FILE gets a CSV k,freq,psd,psd_db (psd_db is nan in a bin
@@ -165,7 +167,9 @@ int main(int argc, char **argv) {
     int k = 31, nv = 8, seeds = 1, gpus = 1, json = 0, steps = 5, multi = 0, staged = -1, search_k = 0;
     unsigned long long search_seed = 1, search_count = 65536;
     std::string outfile;
-    std::string eyefile, specfile;
+    std::string eyefile, specfile, ncofile;
+    unsigned long nco_fcw = 1ul << 20, nco_am = 1ul << 14;      // NCOTest's resets (gateware/top.py:54-55)
+    double nco_samples = 1e6;
     int lags = 256;
     int shape = 16, eye_shift = 4;
     double eye_samples = 1e6;
@@ -201,6 +205,10 @@ int main(int argc, char **argv) {
         else if (a == "--out") outfile = v;
         else if (a == "--eye") eyefile = v;
         else if (a == "--spectrum") specfile = v;
+        else if (a == "--nco") ncofile = v;
+        else if (a == "--fcw") nco_fcw = std::strtoul(v, nullptr, 0);
+        else if (a == "--am") nco_am = std::strtoul(v, nullptr, 0);
+        else if (a == "--nco-samples") nco_samples = std::atof(v);
         else if (a == "--lags") lags = std::atoi(v);
         else if (a == "--eye-samples") eye_samples = std::atof(v);
         else if (a == "--shape") shape = std::atoi(v);
@@ -223,6 +231,41 @@ int main(int argc, char **argv) {
     int ndev_seen = 0;
     CHECK(bbb_device_count(&ndev_seen));
     if (gpus > ndev_seen) { std::fprintf(stderr, "--gpus %d but %d device(s) visible\n", gpus, ndev_seen); return 1; }
+
+    // ---- the NCO's tone (gateware/bbb/nco.py; NCOTest, gateware/top.py:38-61, with fm held at 0) ----------------------------
+    // Writes little-endian int16, the `<h` samples software/memdump reads.
+    if (!ncofile.empty()) {
+        if (nco_samples < 1 || nco_fcw >= (1ul << 24) || nco_am >= (1ul << 16)) {
+            std::fprintf(stderr, "--nco-samples >= 1, --fcw < 2^24, --am < 2^16\n");
+            return 2;
+        }
+        const uint64_t n = (uint64_t)nco_samples;
+        const bbb_nco_cfg cfg = {(uint32_t)nco_fcw, (uint32_t)nco_am, 0, 0};
+        bbb_nco *o = nullptr;
+        int16_t *x = nullptr;
+        CHECK(bbb_nco_open(&cfg, 0, nullptr, &o));
+        if (hipMalloc((void **)&x, n * sizeof(int16_t)) != hipSuccess) { std::fprintf(stderr, "hipMalloc failed\n"); return 1; }
+        const double t0 = now_s();
+        CHECK(bbb_nco_run(o, nullptr, nullptr, nullptr, n, x));
+        bbb_nco_state st{};
+        CHECK(bbb_nco_get_state(o, &st));
+        const double dt = now_s() - t0;
+        std::vector<int16_t> h(n);
+        if (hipMemcpy(h.data(), x, n * sizeof(int16_t), hipMemcpyDeviceToHost) != hipSuccess) { std::fprintf(stderr, "copy failed\n"); return 1; }
+        (void)hipFree(x);
+        CHECK(bbb_nco_close(o));
+        std::FILE *f = std::fopen(ncofile.c_str(), "wb");
+        if (!f) { std::fprintf(stderr, "cannot write %s\n", ncofile.c_str()); return 1; }
+        for (uint64_t i = 0; i < n; ++i) {
+            const uint16_t u = (uint16_t)h[i];
+            const unsigned char b[2] = {(unsigned char)(u & 0xFF), (unsigned char)(u >> 8)};
+            std::fwrite(b, 1, 2, f);
+        }
+        std::fclose(f);
+        std::printf("{\"mode\": \"nco\", \"samples\": %llu, \"fcw\": %lu, \"am\": %lu, \"pa\": %u, \"q\": %d, \"w\": %d, \"y\": %d, "
+                    "\"seconds\": %.6f}\n", (unsigned long long)n, nco_fcw, nco_am, st.pa, st.q, st.w, st.y, dt);
+        return 0;
+    }
 
     // ---- matrix search (software/rnghunt/src/bin/rnghunt.rs:13-66) -------------------------------------------------------
     if (search_k > 0) {

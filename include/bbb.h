@@ -506,6 +506,42 @@ int bbb_tx_acf_open(bbb_lutopt *h, const bbb_tx_cfg *cfg, uint32_t nlags, uint64
 int bbb_tx_acf_run(bbb_tx_acf *a, uint64_t first_sample, uint64_t nsamples, int64_t *acf_dev);
 int bbb_tx_acf_close(bbb_tx_acf *a);
 
+/* ---- numerically controlled oscillator: the board's tone source (gateware/bbb/nco.py) ------------------------------ */
+
+/* NCO(fcw, am, fm, pm) with n = 24, m = 10, p = 16 (nco.py:25-44), clocked once per output sample t:
+ *   adr(t) = ((pa >> 14) + pm(t)) mod 1024          pa' = (pa + fcw + fm(t)) mod 2^24
+ *   q' = rom[adr(t)]   w' = q   y' = am(t) * w       x(t) = y >> 16   (arithmetic: y[16:32], nco.py:43)
+ * rom[i] = round_half_even(32767 * sin(2 pi i / 1023)), i = 0 .. 1023 (np.linspace(0, 2 pi, 1024), nco.py:30-31: the
+ * table's period is 1023 steps, rom[0] = rom[1023] = 0).  q is the ROM port's registered output (migen's synchronous read
+ * port), so x(t) = (am(t - 1) * rom[adr(t - 3)]) >> 16 from reset, where the first three outputs are 0 (the latency
+ * test_nco pins, nco.py:47-66).  When each input enters (fm before pa, pm at the address, am at the product) is read from
+ * the module's text; the reference's test pins only constant inputs.
+ * Each input is a constant of the object's cfg or, per call, a device buffer of one value per sample.  Buffer values are
+ * taken modulo their widths: the low 24 bits of fm (two's complement), the low 10 bits of pm; am is uint16 as it is.
+ * cfg ranges (else BBB_EINVAL): fcw < 2^24, am < 2^16, fm in [-2^23, 2^23), pm in [-512, 512). */
+typedef struct { uint32_t fcw; uint32_t am; int32_t fm; int32_t pm; } bbb_nco_cfg;
+/* The module's registers; all 0 = reset.  pa < 2^24, q and w in int16, y any int32. */
+typedef struct { uint32_t pa; int32_t q, w, y; } bbb_nco_state;
+typedef struct bbb_nco bbb_nco;
+/* The ROM (host only, works without a GPU). */
+int bbb_nco_rom(int16_t rom[1024]);
+/* An oscillator in the reset state on `device`, its work ordered on hip_stream.  The object keeps its state on the device,
+ * so that consecutive runs never wait on the host.  A device without gfx950 gives BBB_ENODEV. */
+int bbb_nco_open(const bbb_nco_cfg *cfg, int device, void *hip_stream, bbb_nco **out);
+/* Retune between runs (the state is kept); ordered behind the runs already queued. */
+int bbb_nco_set_cfg(bbb_nco *o, const bbb_nco_cfg *cfg);
+/* Move the object's later work to another stream, behind everything it queued on the old one (as bbb_lutopt_set_stream). */
+int bbb_nco_set_stream(bbb_nco *o, void *hip_stream);
+/* nsamples clocks from the object's state: x_dev[t] = x(t); fm_dev / am_dev / pm_dev give the input of clock t where not
+ * NULL, the cfg's constant where NULL.  Any alignment of the element types; 16-byte aligned buffers take the wide path.
+ * Consecutive runs continue one waveform.  nsamples = 0 is a no-op.  Asynchronous on the object's stream. */
+int bbb_nco_run(bbb_nco *o, const int32_t *fm_dev, const uint16_t *am_dev, const int16_t *pm_dev, uint64_t nsamples,
+                int16_t *x_dev);
+/* The registers after every run queued so far (waits for the object's stream) / replace them (ordered on the stream). */
+int bbb_nco_get_state(bbb_nco *o, bbb_nco_state *st);
+int bbb_nco_set_state(bbb_nco *o, const bbb_nco_state *st);
+int bbb_nco_close(bbb_nco *o);
+
 /* ---- GF(2) helpers (host only; the pieces of software/rnghunt this path leans on) ------------ */
 
 /* Berlekamp-Massey (software/rnghunt/src/berlekamp_massey.rs:5-31): minimal polynomial of the bit
