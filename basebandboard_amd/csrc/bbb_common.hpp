@@ -137,6 +137,18 @@ uint64_t nco_tiles(uint64_t n);
 int nco_launch(const NcoLaunch &a, int grid, hipStream_t st);
 int nco_put_state(const bbb_nco_state &s, bbb_nco_state *dst, hipStream_t st);   // one thread, a plain store
 
+// sinc_kernels.hip: the 16x sinc interpolator (include/bbb.h, bbb_sinc_*)
+struct SincLaunch {                               // one launch: any number of input samples (64-bit indices)
+    const void *in;                               // int8 or int16 samples; in[-1] .. in[-nbefore] readable
+    void *out;                                    // 16 n elements of int8 or int16
+    uint64_t n;
+    uint32_t nbefore;                             // 0..7
+    uint32_t shift;                               // int16 input: x8 = clamp(x >> shift, -128, 127)
+    int vec;                                      // out is 16-byte aligned: 16-byte stores
+    uint32_t words[32];                           // the table as the reference's BRAM words (sinc.py:42-48)
+};
+int sinc_launch(const SincLaunch &a, bool in16, bool out16, int grid, hipStream_t st);
+
 // bbb_api.hip: what the eye object needs of a handle (reads fields only) and the bbb_tx_cfg checks of bbb_tx_fill_i16
 int lutopt_device(const bbb_lutopt *h);
 hipStream_t lutopt_stream(const bbb_lutopt *h);

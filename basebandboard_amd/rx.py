@@ -69,9 +69,22 @@ class RX:
         bits, nbits = self.slice(samples, first_sample, stride)
         return self.prbsdet.run_stream(bits, nbits, want_err=want_err, want_reload=want_reload)
 
-    def eye(self, samples, first_sample=0, eye=None, hist=None):
+    def interpolate(self, samples, shift=4, out_dtype=torch.int16):
+        """The capture at 16 times its sample rate (sinc.SincInterpolator.interpolate, gateware/bbb/sinc.py): an int16 CUDA
+        tensor of 16 * len(samples) values in -102 .. 101.  int16 samples enter as clamp(x >> shift, -128, 127) (4 takes a
+        12-bit sample to the interpolator's 8 bits); int8 samples need shift = 0."""
+        from .sinc import SincInterpolator
+        return SincInterpolator(samples.device.index or 0).interpolate(samples, shift=shift, out_dtype=out_dtype)
+
+    def eye(self, samples, first_sample=0, eye=None, hist=None, interpolate=False, shift=4):
         """Eye histogram of an int16 CUDA tensor (bbb_eye_accumulate_i16): samples[i] is sample number first_sample + i;
-        `eye` an eye.EyeConfig (default 64 columns, shift 4).  Returns hist [256, ncols] uint64 (added to when given)."""
+        `eye` an eye.EyeConfig (default 64 columns, shift 4).  Returns hist [256, ncols] uint64 (added to when given).
+        interpolate=True: the eye of the 16x interpolated capture instead (bbb_sinc_eye_*; int8 or int16 samples entering
+        as in `interpolate`), 16 columns per captured sample; interpolated sample 16 m + c has the number
+        16 * (first_sample + m) + c, and `eye` then defaults to 64 columns at shift 0."""
+        if interpolate:
+            from .sinc import SincInterpolator
+            return SincInterpolator(samples.device.index or 0).eye(samples, first_sample, eye, hist, shift=shift)
         from .eye import capture_eye
         return capture_eye(samples, first_sample, eye, hist)
 
@@ -90,13 +103,20 @@ class RX:
         n = samples.numel() if nfirst is None else int(nfirst)
         return psd(capture_acf(samples, nlags, nfirst), n, **psd_kw)
 
-    def phase_search(self, samples, stride=None, strict=False):
+    def phase_search(self, samples, stride=None, strict=False, interpolate=False, shift=4):
         """Every setting of the reference's `sample_delay` knob (0 .. samples_per_bit - 1; rx.py:19): the
-        detector's totals per phase and the phase with the fewest errors."""
+        detector's totals per phase and the phase with the fewest errors.
+        interpolate=True: the knob in sixteenths of a sample.  The capture (int8 or int16, entering as in `interpolate`)
+        is interpolated to int16 first -- a temporary of 32 bytes per captured sample -- and searched with 16 * stride
+        over 16 * samples_per_bit phases; phase p samples the interpolated stream at p + 16 * stride * j."""
+        if interpolate:
+            samples = self.interpolate(samples, shift=shift)
         if samples.dtype != torch.int16 or not samples.is_cuda or not samples.is_contiguous():
             raise ValueError("samples must be a contiguous int16 CUDA tensor")
         stride = self.samples_per_bit if stride is None else int(stride)
         nph = self.samples_per_bit
+        if interpolate:
+            stride, nph = stride * 16, nph * 16
         st = (_lib.DetectorStats * nph)()
         dev = samples.device.index or 0
         _lib.check(_lib.lib().bbb_rx_phase_search(C.c_void_p(samples.data_ptr()), samples.numel(), stride, nph,

@@ -16,6 +16,10 @@
 //                       setting and phase (bits decided, errors) after a header line
 //          nco:         --nco FILE [--fcw 1048576] [--am 16384] [--nco-samples 1e6]   the NCO's tone (bbb_nco_*), written as
 //                       little-endian int16 samples (software/memdump's `<h` format)
+//          sinc:        --sinc FILE [--eye-samples 1e6] [--prbs 31] [--nv 8] [--shape 16] [--shift 4]   the scope's 16x sinc
+//                       interpolator (bbb_sinc_*; gateware/bbb/sinc.py): one JSON line with the module's 1024 outputs for the
+//                       7-cycle sine of the reference's test, then the eye of a capture at 4 samples per bit (every second
+//                       sample of the transmitter's waveform) after interpolation, 64 columns per bit, to FILE as a PGM
 //          spectrum:    --spectrum FILE [--lags 256] [--eye-samples 1e6] [--prbs 31] [--nv 8] [--shape 16]   autocorrelation
 //                       counters of the transmitter's waveform (bbb_tx_acf_*) and the power spectrum from them (Bartlett lag
 //                       window, mean removed, one-sided, fs = 1): FILE gets a CSV k,freq,psd,psd_db (psd_db is nan in a bin
@@ -167,7 +171,7 @@ int main(int argc, char **argv) {
     int k = 31, nv = 8, seeds = 1, gpus = 1, json = 0, steps = 5, multi = 0, staged = -1, search_k = 0;
     unsigned long long search_seed = 1, search_count = 65536;
     std::string outfile;
-    std::string eyefile, specfile, ncofile;
+    std::string eyefile, specfile, ncofile, sincfile;
     unsigned long nco_fcw = 1ul << 20, nco_am = 1ul << 14;      // NCOTest's resets (gateware/top.py:54-55)
     double nco_samples = 1e6;
     int lags = 256;
@@ -206,6 +210,7 @@ int main(int argc, char **argv) {
         else if (a == "--eye") eyefile = v;
         else if (a == "--spectrum") specfile = v;
         else if (a == "--nco") ncofile = v;
+        else if (a == "--sinc") sincfile = v;
         else if (a == "--fcw") nco_fcw = std::strtoul(v, nullptr, 0);
         else if (a == "--am") nco_am = std::strtoul(v, nullptr, 0);
         else if (a == "--nco-samples") nco_samples = std::atof(v);
@@ -373,6 +378,85 @@ int main(int argc, char **argv) {
             std::printf("{\"phase\": %d, \"bits\": %llu, \"errors\": %llu, \"ber\": %.6e}\n", p, (unsigned long long)nb,
                         (unsigned long long)ne, nb ? (double)ne / (double)nb : 0.0);
         }
+        return 0;
+    }
+
+    // ---- the scope's sinc interpolator (gateware/bbb/sinc.py) ---------------------------------------------------------------
+    if (!sincfile.empty()) {
+        if (shape < 0 || shape > 31 || eye_samples < 1 || eye_shift < 0 || eye_shift > 15) {
+            std::fprintf(stderr, "--shape 0..31, --eye-samples >= 1, --shift 0..15\n");
+            return 2;
+        }
+        // the module's batch: 72 samples of a 7-cycle sine (gateware/bbb/tests/test_sinc.py:22), outputs y[109 .. 1132]
+        int8_t x[72];
+        for (int i = 0; i < 72; i++) x[i] = (int8_t)(std::sin(2.0 * M_PI * 7.0 * (i == 71 ? 1.0 : i * (1.0 / 71.0))) * 127.0);
+        int8_t *xd = nullptr, *yd = nullptr;
+        if (hipMalloc((void **)&xd, sizeof x) != hipSuccess || hipMalloc((void **)&yd, 72 * BBB_SINC_UP) != hipSuccess ||
+            hipMemcpy(xd, x, sizeof x, hipMemcpyHostToDevice) != hipSuccess) {
+            std::fprintf(stderr, "hipMalloc failed\n");
+            return 1;
+        }
+        const bbb_sinc_cfg c8{1, 1, 0};
+        CHECK(bbb_sinc_interpolate(xd, 72, 0, &c8, yd, 0, nullptr));
+        int8_t y[72 * BBB_SINC_UP];
+        if (hipMemcpy(y, yd, sizeof y, hipMemcpyDeviceToHost) != hipSuccess) { std::fprintf(stderr, "hipMemcpy failed\n"); return 1; }
+        (void)hipFree(xd);
+        (void)hipFree(yd);
+        std::printf("{\"mode\": \"sinc\", \"batch\": [");
+        for (int i = 0; i < 1024; i++) std::printf("%s%d", i ? ", " : "", y[109 + i]);
+        std::printf("]}\n");
+        // a capture at 4 samples per bit: every second sample of the transmitter's waveform (8 per bit), interpolated 16x
+        bbb_tx_cfg cfg{};
+        rcf_taps(shape == 31 ? 1.0 : shape * (1.0 / 31), cfg.coeffs);
+        cfg.source = 0;
+        cfg.prbs_k = k;
+        cfg.prbs_state = 1;
+        cfg.bit_en = 1;
+        cfg.noise_en = 1;
+        cfg.noise_var = nv;
+        cfg.warmup = 16;
+        const uint64_t init[8] = {init0, 0, 0, 0, 0, 0, 0, 0};
+        bbb_lutopt *h = nullptr;
+        CHECK(bbb_lutopt_create(&h, m.n, m.taps.data(), m.off.data(), init, 0));
+        const uint64_t ntx = (uint64_t)eye_samples & ~1ull, ncap = ntx / 2;
+        const size_t nh = 256 * 64;
+        int16_t *w = nullptr;
+        uint64_t *d = nullptr;
+        if (hipMalloc((void **)&w, (ntx + 8) * sizeof(int16_t)) != hipSuccess || hipMalloc((void **)&d, nh * sizeof(uint64_t)) != hipSuccess ||
+            hipMemset(d, 0, nh * sizeof(uint64_t)) != hipSuccess) {
+            std::fprintf(stderr, "hipMalloc failed\n");
+            return 1;
+        }
+        CHECK(bbb_tx_fill_i16(h, &cfg, w, ntx, 0));
+        std::vector<int16_t> tx(ntx), cap(ncap);
+        if (hipMemcpy(tx.data(), w, ntx * sizeof(int16_t), hipMemcpyDeviceToHost) != hipSuccess) { std::fprintf(stderr, "hipMemcpy failed\n"); return 1; }
+        for (uint64_t i = 0; i < ncap; i++) cap[i] = tx[2 * i];
+        if (hipMemcpy(w, cap.data(), ncap * sizeof(int16_t), hipMemcpyHostToDevice) != hipSuccess) { std::fprintf(stderr, "hipMemcpy failed\n"); return 1; }
+        // transmitter sample 2i is captured sample i: bit m peaks at sample 8m + 49, interpolated sample 64m + 392
+        const bbb_sinc_cfg c16{2, 2, (uint32_t)eye_shift};
+        const bbb_eye_cfg eye{64, 0, 392 - 32, 0, 0};
+        bbb_sinc_eye *e = nullptr;
+        CHECK(bbb_sinc_eye_open(&c16, &eye, 0, 0, nullptr, &e));
+        const double t0 = now_s();
+        CHECK(bbb_sinc_eye_run(e, w, ncap, 0, 0, d));
+        std::vector<uint64_t> out(nh);
+        if (hipMemcpy(out.data(), d, nh * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) { std::fprintf(stderr, "hipMemcpy failed\n"); return 1; }
+        const double secs = now_s() - t0;
+        CHECK(bbb_sinc_eye_close(e));
+        CHECK(bbb_lutopt_destroy(h));
+        (void)hipFree(w);
+        (void)hipFree(d);
+        FILE *f = std::fopen(sincfile.c_str(), "wb");
+        if (!f) { std::fprintf(stderr, "cannot write %s\n", sincfile.c_str()); return 1; }
+        std::fprintf(f, "P5\n64 256\n255\n");
+        std::vector<unsigned char> img(nh);
+        uint64_t total = 0;
+        for (size_t i = 0; i < nh; i++) { img[i] = out[i] ? 255 : 0; total += out[i]; }
+        const bool ok = std::fwrite(img.data(), 1, nh, f) == nh;
+        if (std::fclose(f) != 0 || !ok) { std::fprintf(stderr, "cannot write %s\n", sincfile.c_str()); return 1; }
+        std::printf("{\"mode\": \"sinc-eye\", \"captured\": %llu, \"interpolated\": %llu, \"prbs\": %d, \"nv\": %d, \"shape\": %d, "
+                    "\"shift\": %d, \"seconds\": %.4f, \"pgm\": \"%s\"}\n", (unsigned long long)ncap, (unsigned long long)total, k, nv,
+                    shape, eye_shift, secs, sincfile.c_str());
         return 0;
     }
 

@@ -542,6 +542,49 @@ int bbb_nco_get_state(bbb_nco *o, bbb_nco_state *st);
 int bbb_nco_set_state(bbb_nco *o, const bbb_nco_state *st);
 int bbb_nco_close(bbb_nco *o);
 
+/* ---- 16x sinc interpolator: the scope's SincInterpolator (gateware/bbb/sinc.py) -------------------------------------- */
+
+/* 16 output samples per input sample through an 8-tap polyphase windowed sinc (sinc.py:12-49, 91-98):
+ *   h[k] = trunc_toward_zero(127 * sinc(t_k) * hamming_k), t = linspace(-4, 4, 128), symmetric 128-point Hamming window, int8
+ *   acc(m, c)   = sum_{i=0..7} h[16 i + c] * x[m - i]       m >= 0 the input sample, c = 0..15 the phase;
+ *                                                           x[j] = 0 before the start of the record
+ *   y[16 m + c] = int8(acc(m, c) >> 8)                      arithmetic shift
+ * The module's 16-bit adders never wrap (max_c sum_i |h[16 i + c]| = 203, so |acc| <= 25 984) and y lies in -102 .. 101.
+ * The DC gain per phase is 125/256 or 126/256: the reference halves the amplitude, and so does this.
+ * The module itself (72 inputs with no history in, 1024 samples out, as test_sinc pins it) is y[109 .. 1132]. */
+#define BBB_SINC_UP   16      /* output samples per input sample */
+#define BBB_SINC_TAPS 8       /* input samples per output sample */
+/* The table h (host only, works without a GPU).  Tap i of phase c is h[16 i + c]; the reference's BRAM word 2c is
+ * h[c] << 24 | h[16 + c] << 16 | h[32 + c] << 8 | h[48 + c] (bytes), word 2c + 1 the same of h[64 + c ..]. */
+int bbb_sinc_coefficients(int8_t h[128]);
+
+typedef struct {
+    uint32_t in_bytes;    /* 1: int8 samples (sinc.py's port).  2: int16 samples, x8 = clamp(x >> shift, -128, 127), the
+                             row rule of bbb_eye_cfg */
+    uint32_t out_bytes;   /* 1: int8 (the reference's port).  2: the same values as int16, for bbb_eye_accumulate_i16,
+                             bbb_acf_accumulate_i16, bbb_rx_slice, bbb_rx_phase_search */
+    uint32_t shift;       /* 0..15 with in_bytes = 2; must be 0 with in_bytes = 1 */
+} bbb_sinc_cfg;
+
+/* out_dev[16 m + c] = y[16 m + c] for m in [0, nin): 16 nin elements of out_bytes each.  in_dev[-1] .. in_dev[-nbefore]
+ * (elements) must be readable and are the record's earlier samples (only the nearest 7 are used); history beyond them is
+ * 0, so a call that is given the 7 samples in front of its first input continues the stream exactly.  Any element
+ * alignment of both pointers; an out_dev aligned to 16 bytes takes the wide stores.  nin = 0 is a no-op.  Asynchronous
+ * on hip_stream. */
+int bbb_sinc_interpolate(const void *in_dev, uint64_t nin, uint32_t nbefore, const bbb_sinc_cfg *cfg, void *out_dev,
+                         int device, void *hip_stream);
+
+/* The eye of the interpolated record without handing it to the caller: exactly what bbb_eye_accumulate_i16(eye) counts
+ * over the int16 interpolated stream whose sample number is 16 * (first_sample + m) + c.  run works chunk by chunk
+ * through a buffer the object owns (chunk_in input samples, at most 2^27; 0: 2^24, 512 MiB of int16) on hip_stream;
+ * hist_dev ([256][ncols] uint64) is added to.  cfg->out_bytes is ignored.  first_sample + nin <= 2^58. */
+typedef struct bbb_sinc_eye bbb_sinc_eye;
+int bbb_sinc_eye_open(const bbb_sinc_cfg *cfg, const bbb_eye_cfg *eye, uint64_t chunk_in, int device, void *hip_stream,
+                      bbb_sinc_eye **out);
+int bbb_sinc_eye_run(bbb_sinc_eye *e, const void *in_dev, uint64_t nin, uint32_t nbefore, uint64_t first_sample,
+                     uint64_t *hist_dev);
+int bbb_sinc_eye_close(bbb_sinc_eye *e);
+
 /* ---- GF(2) helpers (host only; the pieces of software/rnghunt this path leans on) ------------ */
 
 /* Berlekamp-Massey (software/rnghunt/src/berlekamp_massey.rs:5-31): minimal polynomial of the bit
