@@ -809,7 +809,9 @@ det_chunk_kernel(int mode, const u64 *__restrict src, u64 nbits, u64 nwords, u64
 // (list <- chunks whose speculative start differs from the end of their predecessor: in det_reduce_kernel)
 
 // exact serial continuation from chunk c0 to the end, one lane (guard for streams on which the
-// speculation keeps failing; never taken in the tests' regimes)
+// speculation keeps failing: more than 32 repair passes.  Noise, bursts and all-zero stretches never get there -- every
+// machine reloads from the same bits and the chain settles in one pass; a stream on which the true machine stays locked
+// while no reload can succeed does: tests/test_gpu_detector_stream.py::test_serial_guard_is_reached)
 template <int K>
 __global__ void __launch_bounds__(64)
 det_serial_kernel(const u64 *__restrict src, u64 nbits, u64 nwords, u64 chunk_words, u64 nchunks, u64 c0,

@@ -211,14 +211,19 @@ int bbb_prbs_detector_run(int k, const uint8_t *bits_dev, uint64_t nstreams, uin
  * hand-off).  bits_packed_dev: input wire during clock t at word t/64, bit t%64 (the layout
  * bbb_prbs_fill / bbb_rx_slice write).  err_packed_dev / reload_packed_dev (either may be NULL,
  * ceil(nbits/64) words): `err` / `reload` sampled after clock t, same packing.  The stream is cut
- * into chunks of chunk_bits (0: 4096 ... 32768 by the length; a multiple of 64), each run by one GPU lane from a
+ * into chunks of chunk_bits (a multiple of 64; 0: chosen by the length -- 4096 ... 32768 bits up to 8.6e9 bits, beyond that
+ * 512 ... 1024 words, whichever spreads the blocks of 256 chunks most evenly over the device's CUs: 640 words for 1e10 bits on
+ * 256 CUs), each run by one GPU lane from a
  * speculative state obtained by running the reset detector over the warm_bits (0: 1024) before the
  * chunk; every chunk whose speculative start differs from its predecessor's true end state is run
  * again from that state until the chain is consistent, so the outputs equal the serial machine's
  * bit for bit (prbs.py:61-99).  (A re-run stops where its state meets the speculative run's: from there on the chunk
  * is what the first pass made of it.)  *stats is a host result (the call synchronises the stream).  The call's device
  * workspace (72 bytes per chunk: 22 MB at 1e10 bits; kept up to 256 MiB) and a pinned read-back buffer stay allocated
- * between calls, one set per device and concurrent call. */
+ * between calls, one set per device and concurrent call.
+ * Alignment: the three pointers need 8 bytes, no more.  An input aligned to 16 bytes selects the sparse forms (k != 20: the
+ * stream is classified at memory speed and the machine runs only where it has to); an input at 8 mod 16 bytes is run by the
+ * dense pass, lane by lane -- the same result, several times slower.  The alignment of the outputs selects nothing. */
 typedef struct {
     uint64_t bits;            /* clocks processed */
     uint64_t errors;          /* clocks with err == 1 and reload == 0 (what the reference test compares, prbs.py:152-163) */

@@ -2,9 +2,13 @@
 (bbb_prbs_detector_stream), against the serial restatement of gateware/bbb/prbs.py:61-99.  Every
 err / reload bit and every total must be identical, whatever the chunking and however bad the
 speculative starts are."""
+import time
+
 import numpy as np
 import pytest
 import torch
+
+from detector_geometry import default_chunk_words, form_of
 
 pytestmark = pytest.mark.gpu
 
@@ -90,12 +94,36 @@ def test_noise_input_still_exact(gpu, oracle, k):
 
 
 def test_serial_guard_path(gpu, oracle):
-    """All-zero input after a PRBS prefix with no warm-up at all: whatever the repair passes do, the
-    result must be exact (exercises the many-pass / serial continuation logic)."""
+    """All-zero input after a PRBS prefix with a one-word warm-up: the result must be exact.  (The name is history: this
+    stream never reaches the serial guard, nor even a repair pass -- an all-zero LFSR predicts zeros, so every chunk of the
+    zero stretch is flagged clean and starts consistent; chunks_rerun and serial_fallback are 0, asserted here so that the
+    docstring cannot drift again.  test_serial_guard_is_reached below is the one that gets there.)"""
     k, nbits = 15, 200_000
     words = gpu.PRBS(k).generate(nbits).cpu().numpy().view(np.uint64).copy()
     words[100:] = 0
-    run_both(gpu, oracle, k, words, nbits, chunk_bits=64, warm_bits=64)
+    got = run_both(gpu, oracle, k, words, nbits, chunk_bits=64, warm_bits=64)
+    print(f"\nzeros after a prefix: chunks={got['chunks']} rerun={got['chunks_rerun']} serial_fallback={got['serial_fallback']}", end="")
+    assert got["serial_fallback"] == 0 and got["chunks_rerun"] == 0
+
+
+@pytest.mark.parametrize("k", (7, 20))
+def test_serial_guard_is_reached(gpu, oracle, k):
+    """The cheapest stream on which the speculation never settles: a clean prefix (the serial machine locks), then one
+    flipped bit every k clocks for ever.  The true machine stays locked -- one error per k clocks is far below the
+    threshold -- but every reload of k + k // 2 clocks takes a flipped bit into the LFSR, so no machine started from reset
+    inside that stretch ever locks: every speculative start is wrong, every end state computed from one is wrong, a repair
+    pass puts right exactly one more chunk, and after 32 passes det_serial_kernel takes over (sparse form for k = 7, dense
+    for k = 20)."""
+    nbits = 64 * 64 * 40 + 11
+    words = gpu.PRBS(k).generate(nbits).cpu().numpy().view(np.uint64).copy()
+    pos = np.arange(4096, nbits, k, dtype=np.uint64)
+    np.bitwise_xor.at(words, (pos // np.uint64(64)).astype(np.int64), np.uint64(1) << (pos % np.uint64(64)))
+    clean = oracle.prbs_detector_packed(k, gpu.PRBS(k).generate(nbits).cpu().numpy().view(np.uint64), nbits)[2]
+    st = oracle.prbs_detector_packed(k, words, nbits)[2]
+    assert st["resyncs"] == clean["resyncs"] and st["errors"] == len(pos)      # (on the oracle alone: the true machine stays locked)
+    got = run_both(gpu, oracle, k, words, nbits, chunk_bits=4096, warm_bits=64)
+    print(f"\nk={k}: chunks={got['chunks']} rerun={got['chunks_rerun']} serial_fallback={got['serial_fallback']}", end="")
+    assert got["chunks"] == 41 and got["serial_fallback"] == 1
 
 
 def test_empty_and_errors(gpu):
@@ -119,3 +147,49 @@ def test_full_size_loopback(gpu):
     buf[5_000_000] ^= 1 << 17
     got = gpu.PRBSErrorDetector(31).run_stream(buf, nbits)
     assert got["errors"] == 1 and got["resyncs"] == base
+
+
+MID_NBITS = 2_120_000_000                 # the shortest round length whose DEFAULT chunk (128 words) takes the fused kernel
+
+
+# (k = 7, 9, 23: the oracle passes of all six k != 20 together -- 15-19 s each on one core -- cost more than the pass over
+# 1e10 bits in test_gpu_prbs.py, which is this check for k = 31; k = 11 and 15 share NH = 2 with 23 and go through the
+# fused kernel in test_gpu_detector_forms.py)
+@pytest.mark.parametrize("k", (7, 9, 23))
+def test_default_geometry_takes_the_fused_kernel_exactly(gpu, oracle, k):
+    """One default call (chunk_bits = 0, warm_bits = 0) per k at a length whose default chunk is a fused one -- what a user
+    gets at scale: isolated flips around chunk starts and wave regions; totals and err words exact.  The same call on the
+    clean stream is timed and printed (not asserted): a k whose classification never set a flag would still be exact, and
+    an order of magnitude slower than k = 31."""
+    nbits, nw = MID_NBITS, (MID_NBITS + 63) // 64
+    cw = default_chunk_words(nbits, torch.cuda.get_device_properties(0).multi_processor_count)
+    assert cw == 128 and form_of(k, cw, 1024) == "fused"
+    det = gpu.PRBSErrorDetector(k)
+    buf = gpu.PRBS(k).generate(nbits)
+    clean = det.run_stream(buf, nbits)
+    assert clean["errors"] == 0 and clean["chunks_rerun"] == 0 and clean["chunks"] == -(-nw // cw) and clean["serial_fallback"] == 0
+    ms = []
+    for _ in range(3):
+        t0 = time.perf_counter()
+        det.run_stream(buf, nbits)
+        ms.append((time.perf_counter() - t0) * 1e3)
+    rng = np.random.default_rng(77 + k)
+    lm = np.unique(np.concatenate([rng.integers(2, nw // 128 - 1, size=2000) * 128, rng.integers(1, nw // 8192, size=2000) * 8192]))
+    wd = lm + rng.integers(-4, 5, size=len(lm))                            # distinct words, more than 100 words apart
+    bit = np.where(rng.random(len(lm)) < 0.3, 63, rng.choice((0, 1, 31, 32, 62), size=len(lm)))
+    dv = lambda a: torch.from_numpy(np.asarray(a, dtype=np.int64)).cuda()  # noqa: E731
+    buf[dv(wd)] ^= torch.ones(len(lm), dtype=torch.int64, device="cuda") << dv(bit)
+    words = buf.cpu().numpy().view(np.uint64)
+    t0 = time.perf_counter()
+    e, r, st = oracle.prbs_detector_packed(k, words, nbits)
+    t_oracle = time.perf_counter() - t0
+    assert st["errors"] == len(lm) and st["resyncs"] == clean["resyncs"]   # (the oracle alone: every flip flagged once, still locked)
+    got = det.run_stream(buf, nbits, want_err=True)
+    print(f"\nk={k}: clean default call {min(ms):.3f} ms (host wall, best of 3), chunks={got['chunks']} rerun={got['chunks_rerun']}, "
+          f"oracle pass {t_oracle:.1f} s", end="")
+    for name in TOTALS:
+        assert got[name] == st[name], (name, got[name], st[name])
+    assert got["bits"] == nbits and got["chunks"] == -(-nw // cw) and got["serial_fallback"] == 0
+    del r
+    diff = np.flatnonzero(got["err"].cpu().numpy().view(np.uint64) != e)
+    assert len(diff) == 0, f"err differs from the oracle in {len(diff)} words, first word {diff[0]} = chunk {diff[0] // cw} + {diff[0] % cw}"

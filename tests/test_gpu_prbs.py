@@ -1,7 +1,11 @@
 """PRBS kernels vs the oracle and the golden vectors (through the C ABI).  Bit exact."""
+import time
+
 import numpy as np
 import pytest
 import torch
+
+from detector_geometry import default_chunk_words, form_of
 
 pytestmark = pytest.mark.gpu
 
@@ -168,9 +172,27 @@ def test_baseline_config3_full_size_with_error_mask(gpu, oracle):
     buf2 ^= flip
     del flip
     assert det.count_errors(buf2, nbits) == pos.numel() == 10_000
-    st = det.run_stream(buf2, nbits)
+    # ... and the self-synchronising detector in its DEFAULT geometry at this length -- the fused kernel, what the benchmark
+    # times -- against the oracle's serial machine over the same 1.25 GB: every total and every err word
+    st = det.run_stream(buf2, nbits, want_err=True)
     first_in_reload = 1 if st["reload_clocks"] > 0 else 0                  # bit 0 arrives during the reload out of reset
     assert st["errors_raw"] + 0 >= 10_000 - first_in_reload and st["errors"] in (10_000, 10_000 - first_in_reload)
+    nwords = (nbits + 63) // 64
+    cw = default_chunk_words(nbits, torch.cuda.get_device_properties(buf2.device).multi_processor_count)
+    assert 512 <= cw <= 1024 and form_of(31, cw, 1024) == "fused"          # (640 words on 256 CUs)
+    assert st["chunks"] == -(-nwords // cw) and st["serial_fallback"] == 0
+    words = buf2.cpu().numpy().view(np.uint64)
+    t0 = time.perf_counter()
+    e, r, ost = oracle.prbs_detector_packed(31, words, nbits)
+    print(f"\noracle detector pass over {nbits} bits: {time.perf_counter() - t0:.1f} s; chunks={st['chunks']} of {cw} words, "
+          f"rerun={st['chunks_rerun']}", end="")
+    del r, words
+    for name in ("errors", "errors_raw", "reload_clocks", "resyncs"):
+        assert st[name] == ost[name], (name, st[name], ost[name])
+    assert st["bits"] == nbits
+    e_t = torch.from_numpy(e.view(np.int64))
+    for lo in range(0, nwords, piece):
+        assert torch.equal(st["err"][lo: lo + piece].cpu(), e_t[lo: lo + piece]), f"err differs from the oracle in words [{lo}, {lo + piece})"
 
 
 def test_concurrent_checks_do_not_share_a_counter(gpu, oracle):
