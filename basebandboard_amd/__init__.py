@@ -15,4 +15,6 @@ from .txsweep import TxSetting, TxBerSweep                 # noqa: F401
 from .spectrum import TxAcf, capture_acf, tx_acf, psd, MAX_LAGS  # noqa: F401
 from .nco import NCO, NCOState                           # noqa: F401
 from .sinc import SincInterpolator                       # noqa: F401
-from . import gf2, recurrences                           # noqa: F401
+from .grngstats import (clt_pmf, clt_pmf_delivered, moments, chi_square, tail_table, pdf_cdf, evaluate,  # noqa: F401
+                        evaluate_samples)
+from . import gf2, recurrences, grngstats                # noqa: F401

@@ -2180,4 +2180,34 @@ namespace bbb {
 int lutopt_device(const bbb_lutopt *h) { return h->device; }
 hipStream_t lutopt_stream(const bbb_lutopt *h) { return h->stream; }
 int tx_cfg_check(const bbb_tx_cfg *cfg) { return tx_check(cfg); }
+
+// what bbb_awgn_hist (hist_api.hip) needs of a handle
+int lutopt_k(const bbb_lutopt *h) { return h->k; }
+int lutopt_staged_level(const bbb_lutopt *h) { return h->staged_level; }
+
+// The staged form of bbb_awgn_fill_i8(nsamples, first_step) on the shipped n256 matrix with the CALLER's kernel in the byte
+// mover's place: the sample kernel (small form, as at one read per kernel) leaves the count planes in the next staging slot
+// and `visit` queues its reader on the stream it is given -- the caller's, behind the slot's sample kernel, under the slot's
+// events like every mover (queue_mover_with).  Nothing is delivered; a look-ahead half that waited in the slot is dropped.
+int lutopt_stage_visit(bbb_lutopt *h, uint64_t nsamples, uint64_t first_step, lutopt_stage_visitor visit, void *ctx) {
+    if (!h || !visit) return fail(BBB_EINVAL, "null argument");
+    if (!h->specialised || h->device < 0) return fail(BBB_EUNSUP, "the staged sample kernel exists for the shipped n256 matrix on a device");
+    if (nsamples == 0 || first_step + nsamples < first_step) return fail(BBB_EINVAL, "empty range, or first_step + nsamples overflows");
+    BBB_HIP(hipSetDevice(h->device));
+    uint64_t L, G;
+    unsigned nlanes;
+    partition(h, nsamples, 16, &L, &G, &nlanes);
+    if (L > 0xffffff00ull) return fail(BBB_EINVAL, "nsamples too large for one call (segment length must fit 32 bits): split it");
+    h->last_fill_tx = false;
+    const uint64_t seed_step = first_step + 1;            // the small form takes the state OF its first sample
+    int rc = begin_op(h, true, h->pf.matches(seed_step, L, G));
+    if (rc) return rc;
+    bool from_pf = false;
+    if ((rc = acquire_planes(h, seed_step, L, G, nlanes, true, &from_pf))) return rc;
+    int slot = 0;
+    if ((rc = produce_planes(h, L, nlanes, nullptr, from_pf, &slot, true))) return rc;
+    return queue_mover_with(h, slot, [&](const void *stage, hipStream_t ms) {
+        return visit(ctx, stage, nsamples, (unsigned)L, G, nlanes, ms);
+    });
+}
 }  // namespace bbb

@@ -153,5 +153,24 @@ int sinc_launch(const SincLaunch &a, bool in16, bool out16, int grid, hipStream_
 int lutopt_device(const bbb_lutopt *h);
 hipStream_t lutopt_stream(const bbb_lutopt *h);
 int tx_cfg_check(const bbb_tx_cfg *cfg);
+// ... and what bbb_awgn_hist needs: two more fields, and the staged sample kernel of a range with the caller's kernel as the reader
+// of its staging slot (`visit` queues that kernel on the stream it is given; the scheduler's events stay in bbb_api.hip)
+int lutopt_k(const bbb_lutopt *h);
+int lutopt_staged_level(const bbb_lutopt *h);
+typedef int (*lutopt_stage_visitor)(void *ctx, const void *stage, uint64_t nsamples, unsigned L, uint64_t G, unsigned nlanes, hipStream_t st);
+int lutopt_stage_visit(bbb_lutopt *h, uint64_t nsamples, uint64_t first_step, lutopt_stage_visitor visit, void *ctx);
+
+// hist_kernels.hip: the histogram of the CLTGRNG samples (include/bbb.h, bbb_awgn_hist)
+constexpr unsigned kHistMaxBins = 512;
+// blocks a histogram launch may use on the current device (or a negative BBB_E* code); the scratch is blocks x nbins u32
+int hist_grid_blocks();
+// bins the samples [0, nsamples) of the count planes a staged sample kernel left (256 bins), one partial per block
+int hist_planes_launch(const void *stage, uint64_t nsamples, unsigned L, unsigned nlanes, uint32_t *scratch, int blocks, unsigned *used,
+                       hipStream_t st);
+// bins int8 (elem 1) or int16 (elem 2) samples of a k-bin generator: bin = (x + nbins / 2) mod nbins; nsamples <= 2^31
+int hist_samples_launch(const void *samples, int elem, uint64_t nsamples, unsigned nbins, uint32_t *scratch, int blocks, unsigned *used,
+                        hipStream_t st);
+// hist[b] += the `used` partials
+int hist_reduce_launch(const uint32_t *scratch, unsigned used, unsigned nbins, uint64_t *hist, hipStream_t st);
 
 }  // namespace bbb

@@ -223,6 +223,22 @@ class CLTGRNG:
         _lib.check(fn(u._h, C.c_void_p(out.data_ptr()), int(nsamples), int(first_step)), "bbb_awgn_fill")
         return out[:nsamples]
 
+    def histogram(self, nsamples, first_step=0, out=None):
+        """The histogram of `generate(nsamples, first_step)` without the samples (bbb_awgn_hist): a uint64 CUDA tensor of n
+        bins, bin x + n/2 for the delivered sample x (the tree value +n/2 wraps to -n/2: bin 0).  ADDS into `out` if one
+        is given (uint64 or int64, n elements), so a range may be cut into calls.  Asynchronous on the current torch
+        stream.  basebandboard_amd.grngstats evaluates the counts against the exact law."""
+        u = self.urng
+        dev = torch.device("cuda", u.device)
+        if out is None:
+            out = torch.zeros(self.n, dtype=torch.uint64, device=dev)
+        if (out.dtype not in (torch.uint64, torch.int64) or tuple(out.shape) != (self.n,) or not out.is_contiguous()
+                or out.device != dev):
+            raise ValueError(f"out must be a contiguous uint64 (or int64) tensor of {self.n} elements on {dev}")
+        u._bind_stream()
+        _lib.check(_lib.lib().bbb_awgn_hist(u._h, C.c_void_p(out.data_ptr()), int(nsamples), int(first_step)), "bbb_awgn_hist")
+        return out
+
     def prefetch(self, nsamples, first_step=0):
         """Announce the next `generate(nsamples, first_step)`: its start states are derived now, on a
         side stream, beside whatever the GPU is running.  Purely a performance hint."""

@@ -24,6 +24,11 @@
 //                       counters of the transmitter's waveform (bbb_tx_acf_*) and the power spectrum from them (Bartlett lag
 //                       window, mean removed, one-sided, fs = 1): FILE gets a CSV k,freq,psd,psd_db (psd_db is nan in a bin
 //                       where the finite-record estimate dips below zero); one JSON line with the counters
+//          grng eval:   --grng-eval N [--first-step S]   the evaluation of software/clt-grng/clt-grng-evaluate.py:18-31 over N
+//                       samples of the generator's stream from clock S (bbb_awgn_hist in chunks; the samples never leave the
+//                       chip): the reference's two lines (theoretical and sample mean and variance, from the counters, in
+//                       double), then one JSON line with the counters' total, the lowest and highest occupied bin and the
+//                       elapsed milliseconds
 //          search:      --search K [--seed S] [--count N] --out FILE    the reference's rnghunt (software/rnghunt/src/bin/
 //                       rnghunt.rs:13-66) on the GPU: candidates of `seed` are examined in windows of N (default 65536)
 //                       until one has period 2^K - 1; it is written to FILE in the reference's `out` format (K lines of K
@@ -179,7 +184,8 @@ int main(int argc, char **argv) {
     double eye_samples = 1e6;
     int tx_sweep = 0, nv_lo = 0, nv_hi = 15;
     unsigned long long init0 = 1;
-    double bits = 1e9, from = 0, to = 10, step = 1, loopback = 0, nsamples = 0;
+    double bits = 1e9, from = 0, to = 10, step = 1, loopback = 0, nsamples = 0, grng_eval = 0;
+    unsigned long long first_step = 0;
     for (int i = 1; i + 1 < argc; i += 2) {
         const std::string a = argv[i];
         const char *v = argv[i + 1];
@@ -197,6 +203,8 @@ int main(int argc, char **argv) {
         }
         else if (a == "--loopback") loopback = std::atof(v);
         else if (a == "--nsamples") nsamples = std::atof(v);
+        else if (a == "--grng-eval") grng_eval = std::atof(v);
+        else if (a == "--first-step") first_step = std::strtoull(v, nullptr, 0);
         else if (a == "--steps") steps = std::atoi(v);
         else if (a == "--gpus") gpus = std::atoi(v);
         else if (a == "--shard") shard = v;
@@ -329,6 +337,48 @@ int main(int argc, char **argv) {
         (void)bbb_lutopt_destroy(hh);
         return rc;
     };
+
+    // ---- the generator's evaluation (software/clt-grng/clt-grng-evaluate.py:18-31) over any number of samples ------------------
+    if (grng_eval >= 1) {
+        const uint64_t n = (uint64_t)grng_eval, chunk = 1ull << 34;
+        if (m.n < 2 || m.n > 512 || (m.n & (m.n - 1))) { std::fprintf(stderr, "--grng-eval needs a power-of-two matrix up to 512\n"); return 2; }
+        const uint64_t init[8] = {init0, 0, 0, 0, 0, 0, 0, 0};
+        bbb_lutopt *h = nullptr;
+        CHECK(bbb_lutopt_create(&h, m.n, m.taps.data(), m.off.data(), init, 0));
+        const size_t nb = (size_t)m.n;
+        uint64_t *d = nullptr;
+        if (hipMalloc((void **)&d, nb * sizeof(uint64_t)) != hipSuccess || hipMemset(d, 0, nb * sizeof(uint64_t)) != hipSuccess) {
+            std::fprintf(stderr, "hipMalloc failed\n");
+            return 1;
+        }
+        const double t0 = now_s();
+        for (uint64_t off = 0; off < n; off += chunk)               // the calls add into the same counters
+            CHECK(bbb_awgn_hist(h, d, n - off < chunk ? n - off : chunk, first_step + off));
+        std::vector<uint64_t> c(nb);
+        if (hipMemcpy(c.data(), d, nb * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) { std::fprintf(stderr, "hipMemcpy failed\n"); return 1; }
+        const double ms = (now_s() - t0) * 1e3;
+        CHECK(bbb_lutopt_destroy(h));
+        (void)hipFree(d);
+        // bin b holds the sample b - n/2; sums in long double, the two lines in double as the reference prints them
+        long double total = 0, s1 = 0, s2 = 0;
+        int lo = -1, hi = -1;
+        for (size_t b = 0; b < nb; b++) {
+            if (!c[b]) continue;
+            const long double x = (long double)b - (long double)(nb / 2);
+            total += (long double)c[b];
+            s1 += x * (long double)c[b];
+            s2 += x * x * (long double)c[b];
+            if (lo < 0) lo = (int)b;
+            hi = (int)b;
+        }
+        const double mean = (double)(s1 / total), var = (double)(s2 / total - (s1 / total) * (s1 / total));
+        std::printf("Theoretical mean \u03bc=%.4e, variance \u03c3\u00b2=%.4e.\n", 0.0, (double)m.n / 4);
+        std::printf("Sample mean \u03bc=%.4e, variance \u03c3\u00b2=%.4e.\n", mean, var);
+        std::printf("{\"mode\": \"grng_eval\", \"n\": %d, \"first_step\": %llu, \"total\": %llu, \"min_bin\": %d, \"max_bin\": %d, "
+                    "\"min_sample\": %d, \"max_sample\": %d, \"elapsed_ms\": %.3f}\n", m.n, first_step, (unsigned long long)total, lo, hi,
+                    lo - (int)(nb / 2), hi - (int)(nb / 2), ms);
+        return 0;
+    }
 
     // ---- eye diagram and bathtub of the transmitter (gateware/bbb/dso.py, drawn by ui.py) -------------------------------
     if (!eyefile.empty()) {

@@ -166,6 +166,23 @@ int bbb_awgn_stream_seek(bbb_awgn_stream *s, uint64_t first_step);
 int bbb_awgn_stream_tell(const bbb_awgn_stream *s, uint64_t *next_step);
 int bbb_awgn_stream_close(bbb_awgn_stream *s);
 
+/* The HISTOGRAM of the sample stream -- the counting half of software/clt-grng/clt-grng-evaluate.py:18-50, over a range of
+ * the stream instead of 100 000 draws, without the samples ever being handed to the caller:
+ *   for every i < nsamples:  hist_dev[x_i + k/2] += 1,   x_i = the sample bbb_awgn_fill_i8 / _i16 delivers at position i of
+ *                                                         (nsamples, first_step)
+ * hist_dev: k uint64 device counters (256 for the n256 generator, 512 for n512), 8-byte aligned.  The bin is that of the
+ * DELIVERED, truncated sample: the tree value +k/2 lands in bin 0, as the log2(k)-bit Signal wraps it to -k/2.
+ * The call ADDS into the counters (as bbb_eye_accumulate_i16): a range may be cut into calls at any point, and a multi-GPU
+ * host reduces the counters with one collective.  Any nsamples (0: nothing is done) and any first_step; a long range is cut
+ * into launches internally, so that every partial count is exact.  Asynchronous on the handle's stream, ordered like a fill;
+ * the handle's staging mode is the same after the call as before (a look-ahead half that waited is dropped, as by
+ * bbb_lutopt_set_staged).  On the shipped n256 matrix pieces of 2^24 samples and more are counted by a guest kernel beside
+ * the sample kernel, straight from its staging buffer (two buffers of up to 1 GiB); every other generator fills an internal
+ * buffer of at most 2^26 samples and counts that.
+ * Errors: BBB_EUNSUP where k is not a power of two, BBB_ENODEV on a host-only handle, BBB_EINVAL for a null or misaligned
+ * pointer. */
+int bbb_awgn_hist(bbb_lutopt *h, uint64_t *hist_dev, uint64_t nsamples, uint64_t first_step);
+
 /* CLTGRNG adder tree on caller-supplied uniform words (the loop body of
  * software/clt-grng/clt-grng-evaluate.py:8-16): states_dev holds nstates states of
  * ceil(k/64) u64 words each; out_dev[i] = un-truncated tree value (int16). */
