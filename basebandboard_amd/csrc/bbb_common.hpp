@@ -149,6 +149,23 @@ struct SincLaunch {                               // one launch: any number of i
 };
 int sinc_launch(const SincLaunch &a, bool in16, bool out16, int grid, hipStream_t st);
 
+// fir_kernels.hip: the exact integer FIR filter (include/bbb.h, bbb_fir_*)
+constexpr int kFirTile = 2048;                    // input samples per workgroup step
+struct FirLaunch {                                // one launch: any number of input samples (64-bit indices)
+    const int16_t *in;                            // in[-1] .. in[-nbefore] readable
+    void *out;                                    // nout int16 or int32, or ceil(nout / 64) zeroed u64 words of decisions
+    uint64_t nin, nout;
+    uint32_t nbefore;                             // 0 .. ntaps - 1
+    uint32_t ngroups;                             // groups of four tap words (eight taps) in use: 1..32
+    uint32_t shift, decim, phase;
+    int32_t threshold;
+    int strict;
+    int in_vec, out_vec;                          // in / out is 16-byte aligned: 16-byte loads / stores
+    uint32_t taps[BBB_FIR_MAX_TAPS / 2];          // word p = h[2p + 1] | h[2p] << 16, zero beyond ntaps
+};
+// mode 0: int16 out (saturating), 1: int32 out, 2: packed decisions against threshold
+int fir_launch(const FirLaunch &a, int mode, int grid, hipStream_t st);
+
 // bbb_api.hip: what the eye object needs of a handle (reads fields only) and the bbb_tx_cfg checks of bbb_tx_fill_i16
 int lutopt_device(const bbb_lutopt *h);
 hipStream_t lutopt_stream(const bbb_lutopt *h);

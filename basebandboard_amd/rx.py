@@ -5,6 +5,8 @@ incoming samples are thresholded to single bits (`~sample[-1]`, rx.py:29), delay
 `sample_delay` samples (BitDelayLine, rx.py:32-33) and handed to a PRBSErrorDetector once per bit.
 Here the sample stream is a tensor in HBM: `slice` returns the decided bits packed 64 per word,
 `count_errors` feeds them to the phase-known checker, `detect` to the exact detector FSM.
+`rx_filter` (a fir.FIR, e.g. FIR.moving_average()) puts the reference's receive filter in front of the decision
+(rx.py:24-26: `MovingAverage(sample)`, `sliced = avg.x > 0`); without it the raw samples are sliced, as before.
 (The reference clocks its detector from bit 1 of a log2(samples_per_bit)-bit counter, i.e. every
 4 samples whatever samples_per_bit is -- rx.py:35-39; `stride` defaults to samples_per_bit, pass 4
 to reproduce that.)
@@ -28,14 +30,21 @@ class RX:
         self.prbs_k, self.samples_per_bit, self.sample_delay, self.device = prbs_k, int(samples_per_bit), int(sample_delay), int(device)
         self.prbsdet = PRBSErrorDetector(prbs_k, device=device)
 
-    def slice(self, samples, first_sample=0, stride=None, strict=False):
+    def slice(self, samples, first_sample=0, stride=None, strict=False, rx_filter=None):
         """Decided bits of an int16 CUDA tensor: bit j = samples[first_sample + sample_delay + j*stride] >= 0
-        (`strict`: > 0, the capture script software/memdump/decode.py:15).  Returns (packed int64 tensor, nbits)."""
+        (`strict`: > 0, the capture script software/memdump/decode.py:15).  Returns (packed int64 tensor, nbits).
+        rx_filter (a fir.FIR): the same indices of the filtered stream instead, acc(..) >= 0 (bbb_fir_slice; the
+        filtered samples are never stored)."""
         if samples.dtype != torch.int16 or not samples.is_cuda or not samples.is_contiguous():
             raise ValueError("samples must be a contiguous int16 CUDA tensor")
         stride = self.samples_per_bit if stride is None else int(stride)
         phase = int(first_sample) + self.sample_delay
         n = samples.numel()
+        if rx_filter is not None:
+            # whole strides in front of the first bit become history, so that the phase handed over is below the stride
+            off = min(phase - phase % stride, n)
+            nb = min(off, len(rx_filter) - 1)
+            return rx_filter.slice(samples[off - nb:], stride=stride, phase=phase % stride, strict=strict, nbefore=nb)
         nbits = (n - phase + stride - 1) // stride if phase < n else 0
         out = torch.empty((nbits + 63) // 64, dtype=torch.int64, device=samples.device)
         nb = C.c_uint64()
@@ -47,26 +56,32 @@ class RX:
         return out, nbits
 
     @staticmethod
-    def decode_capture(raw, stride=4, device=0):
+    def decode_capture(raw, stride=4, device=0, average=False):
         """The reference's capture decoder (software/memdump/decode.py:11-18): `raw` holds little-endian
         int16 ADC samples (it reads 8192 of them from the serial port), every `stride`-th sample is
-        compared against 0 (`dat > 0`) and the bits are returned as a uint8 numpy array."""
+        compared against 0 (`dat > 0`) and the bits are returned as a uint8 numpy array.
+        average=True: software/memdump/adcplot.py:34-36 instead -- lfilter([1, 1, 1, 1], [1], dat), dat[3::stride],
+        dat > 0 (the filter line is commented out there)."""
         import numpy as np
         x = np.frombuffer(bytes(raw), dtype="<i2").astype(np.int16)
         t = torch.from_numpy(x.copy()).to(torch.device("cuda", device))
         rx = RX(7, 1, 0, device=device)
-        bits, nbits = rx.slice(t, stride=stride, strict=True)
+        if average:
+            from .fir import FIR
+            bits, nbits = FIR([1, 1, 1, 1], device=device).slice(t, stride=stride, phase=3, strict=True)
+        else:
+            bits, nbits = rx.slice(t, stride=stride, strict=True)
         return np.unpackbits(bits.cpu().numpy().view(np.uint8), bitorder="little")[:nbits]
 
-    def count_errors(self, samples, first_sample=0, first_bit=0, prbs_init=1, stride=None):
+    def count_errors(self, samples, first_sample=0, first_bit=0, prbs_init=1, stride=None, rx_filter=None):
         """Slice, then count the positions that differ from PRBS-k (started `first_bit` bits after `prbs_init`)."""
-        bits, nbits = self.slice(samples, first_sample, stride)
+        bits, nbits = self.slice(samples, first_sample, stride, rx_filter=rx_filter)
         return self.prbsdet.count_errors(bits, nbits, first_bit=first_bit, init=prbs_init), nbits
 
-    def detect(self, samples, first_sample=0, stride=None, want_err=False, want_reload=False):
+    def detect(self, samples, first_sample=0, stride=None, want_err=False, want_reload=False, rx_filter=None):
         """Slice at this receiver's `sample_delay`, then the exact self-synchronising detector over the
         whole stream (rx.py:41-46 at scale): totals as PRBSErrorDetector.run_stream returns them."""
-        bits, nbits = self.slice(samples, first_sample, stride)
+        bits, nbits = self.slice(samples, first_sample, stride, rx_filter=rx_filter)
         return self.prbsdet.run_stream(bits, nbits, want_err=want_err, want_reload=want_reload)
 
     def interpolate(self, samples, shift=4, out_dtype=torch.int16):
@@ -76,12 +91,15 @@ class RX:
         from .sinc import SincInterpolator
         return SincInterpolator(samples.device.index or 0).interpolate(samples, shift=shift, out_dtype=out_dtype)
 
-    def eye(self, samples, first_sample=0, eye=None, hist=None, interpolate=False, shift=4):
+    def eye(self, samples, first_sample=0, eye=None, hist=None, interpolate=False, shift=4, rx_filter=None):
         """Eye histogram of an int16 CUDA tensor (bbb_eye_accumulate_i16): samples[i] is sample number first_sample + i;
         `eye` an eye.EyeConfig (default 64 columns, shift 4).  Returns hist [256, ncols] uint64 (added to when given).
         interpolate=True: the eye of the 16x interpolated capture instead (bbb_sinc_eye_*; int8 or int16 samples entering
         as in `interpolate`), 16 columns per captured sample; interpolated sample 16 m + c has the number
-        16 * (first_sample + m) + c, and `eye` then defaults to 64 columns at shift 0."""
+        16 * (first_sample + m) + c, and `eye` then defaults to 64 columns at shift 0.
+        rx_filter (a fir.FIR): the eye of rx_filter.filter(samples), an int16 temporary, in the samples' place."""
+        if rx_filter is not None:
+            samples = rx_filter.filter(samples)
         if interpolate:
             from .sinc import SincInterpolator
             return SincInterpolator(samples.device.index or 0).eye(samples, first_sample, eye, hist, shift=shift)
@@ -103,12 +121,15 @@ class RX:
         n = samples.numel() if nfirst is None else int(nfirst)
         return psd(capture_acf(samples, nlags, nfirst), n, **psd_kw)
 
-    def phase_search(self, samples, stride=None, strict=False, interpolate=False, shift=4):
+    def phase_search(self, samples, stride=None, strict=False, interpolate=False, shift=4, rx_filter=None):
         """Every setting of the reference's `sample_delay` knob (0 .. samples_per_bit - 1; rx.py:19): the
         detector's totals per phase and the phase with the fewest errors.
         interpolate=True: the knob in sixteenths of a sample.  The capture (int8 or int16, entering as in `interpolate`)
         is interpolated to int16 first -- a temporary of 32 bytes per captured sample -- and searched with 16 * stride
-        over 16 * samples_per_bit phases; phase p samples the interpolated stream at p + 16 * stride * j."""
+        over 16 * samples_per_bit phases; phase p samples the interpolated stream at p + 16 * stride * j.
+        rx_filter (a fir.FIR): rx_filter.filter(samples), an int16 temporary, is searched in the samples' place."""
+        if rx_filter is not None:
+            samples = rx_filter.filter(samples)
         if interpolate:
             samples = self.interpolate(samples, shift=shift)
         if samples.dtype != torch.int16 or not samples.is_cuda or not samples.is_contiguous():

@@ -20,6 +20,10 @@
 //                       interpolator (bbb_sinc_*; gateware/bbb/sinc.py): one JSON line with the module's 1024 outputs for the
 //                       7-cycle sine of the reference's test, then the eye of a capture at 4 samples per bit (every second
 //                       sample of the transmitter's waveform) after interpolation, 64 columns per bit, to FILE as a PGM
+//          fir:         --fir 1 [--eye-samples 1e6] [--prbs 31] [--nv 8]   the moving-average receiver of gateware/bbb/rx.py:24-26
+//                       (bbb_fir_slice with the taps of bbb_fir_moving_average) beside the plain sign slicer (bbb_rx_slice) over a
+//                       noisy transmission of the 4-sample rectangular pulse (the last set of PRBSShaper.from_rcf), each at 8
+//                       samples per bit into the exact detector: one JSON line with both error counts
 //          spectrum:    --spectrum FILE [--lags 256] [--eye-samples 1e6] [--prbs 31] [--nv 8] [--shape 16]   autocorrelation
 //                       counters of the transmitter's waveform (bbb_tx_acf_*) and the power spectrum from them (Bartlett lag
 //                       window, mean removed, one-sided, fs = 1): FILE gets a CSV k,freq,psd,psd_db (psd_db is nan in a bin
@@ -182,7 +186,7 @@ int main(int argc, char **argv) {
     int lags = 256;
     int shape = 16, eye_shift = 4;
     double eye_samples = 1e6;
-    int tx_sweep = 0, nv_lo = 0, nv_hi = 15;
+    int tx_sweep = 0, nv_lo = 0, nv_hi = 15, fir = 0;
     unsigned long long init0 = 1;
     double bits = 1e9, from = 0, to = 10, step = 1, loopback = 0, nsamples = 0, grng_eval = 0;
     unsigned long long first_step = 0;
@@ -227,6 +231,7 @@ int main(int argc, char **argv) {
         else if (a == "--shape") shape = std::atoi(v);
         else if (a == "--shift") eye_shift = std::atoi(v);
         else if (a == "--tx-sweep") tx_sweep = std::atoi(v);
+        else if (a == "--fir") fir = std::atoi(v);
         else if (a == "--nv-range") {
             if (std::sscanf(v, "%d:%d", &nv_lo, &nv_hi) != 2) { std::fprintf(stderr, "--nv-range A:B\n"); return 2; }
         }
@@ -507,6 +512,53 @@ int main(int argc, char **argv) {
         std::printf("{\"mode\": \"sinc-eye\", \"captured\": %llu, \"interpolated\": %llu, \"prbs\": %d, \"nv\": %d, \"shape\": %d, "
                     "\"shift\": %d, \"seconds\": %.4f, \"pgm\": \"%s\"}\n", (unsigned long long)ncap, (unsigned long long)total, k, nv,
                     shape, eye_shift, secs, sincfile.c_str());
+        return 0;
+    }
+
+    // ---- the moving-average receiver (gateware/bbb/average.py, rx.py:24-26) beside the plain slicer ---------------------------
+    if (fir) {
+        if (eye_samples < 1 || nv < 0 || nv > 15) { std::fprintf(stderr, "--eye-samples >= 1, --nv 0..15\n"); return 2; }
+        bbb_tx_cfg cfg{};
+        for (int i = 30; i < 34; i++) cfg.coeffs[i] = 254;          // the rectangular pulse (bitshaper.py:108)
+        cfg.source = 0;
+        cfg.prbs_k = k;
+        cfg.prbs_state = 1;
+        cfg.bit_en = 1;
+        cfg.noise_en = 1;
+        cfg.noise_var = nv;
+        cfg.warmup = 16;
+        const uint64_t init[8] = {init0, 0, 0, 0, 0, 0, 0, 0};
+        bbb_lutopt *h = nullptr;
+        CHECK(bbb_lutopt_create(&h, m.n, m.taps.data(), m.off.data(), init, 0));
+        const uint64_t ntx = (uint64_t)eye_samples;
+        int16_t *w = nullptr;
+        uint64_t *b = nullptr;
+        if (hipMalloc((void **)&w, ntx * sizeof(int16_t)) != hipSuccess || hipMalloc((void **)&b, (ntx / 8 / 64 + 2) * sizeof(uint64_t)) != hipSuccess) {
+            std::fprintf(stderr, "hipMalloc failed\n");
+            return 1;
+        }
+        CHECK(bbb_tx_fill_i16(h, &cfg, w, ntx, 0));
+        // bit m holds samples 8m + 47 .. 8m + 50: the plain slicer looks at 8m + 48, the running sum of four is complete at 8m + 50
+        uint64_t nplain = 0, nfilt = 0;
+        bbb_detector_stats plain{}, filt{};
+        const double t0 = now_s();
+        CHECK(bbb_rx_slice(w, ntx, 8, 0, 0, b, &nplain, 0, nullptr));
+        CHECK(bbb_prbs_detector_stream(k, b, nplain, nullptr, nullptr, &plain, 0, 0, 0, nullptr));
+        bbb_fir_cfg fc;
+        CHECK(bbb_fir_moving_average(&fc, 0));
+        fc.decim = 8;
+        fc.phase = 2;
+        CHECK(bbb_fir_slice(w, ntx, 0, &fc, 0, 0, b, &nfilt, 0, nullptr));
+        CHECK(bbb_prbs_detector_stream(k, b, nfilt, nullptr, nullptr, &filt, 0, 0, 0, nullptr));
+        const double secs = now_s() - t0;
+        CHECK(bbb_lutopt_destroy(h));
+        (void)hipFree(w);
+        (void)hipFree(b);
+        std::printf("{\"mode\": \"fir\", \"samples\": %llu, \"prbs\": %d, \"nv\": %d, \"plain\": {\"phase\": 0, \"bits\": %llu, \"errors\": %llu, "
+                    "\"reload_clocks\": %llu}, \"moving_average\": {\"phase\": 2, \"bits\": %llu, \"errors\": %llu, \"reload_clocks\": %llu}, "
+                    "\"seconds\": %.4f}\n", (unsigned long long)ntx, k, nv, (unsigned long long)plain.bits, (unsigned long long)plain.errors,
+                    (unsigned long long)plain.reload_clocks, (unsigned long long)filt.bits, (unsigned long long)filt.errors,
+                    (unsigned long long)filt.reload_clocks, secs);
         return 0;
     }
 

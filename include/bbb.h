@@ -607,6 +607,45 @@ int bbb_sinc_eye_run(bbb_sinc_eye *e, const void *in_dev, uint64_t nin, uint32_t
                      uint64_t *hist_dev);
 int bbb_sinc_eye_close(bbb_sinc_eye *e);
 
+/* ---- exact integer FIR filter: receive filter, decimator, filtered slicer (gateware/bbb/average.py, rx.py:24-26) ---- */
+
+/*   acc(n) = sum_{i < ntaps} h[i] * x[n - i]       x[j], j < 0: in_dev[j] while j >= -nbefore, 0 beyond
+ *   y[q]   = sat(acc(phase + q * decim) >> shift)   q in [0, nout), arithmetic shift
+ *   nout   = phase < nin ? (nin - phase + decim - 1) / decim : 0
+ * With sum |h[i]| <= 65535 and int16 samples |acc| <= 65535 * 32768 < 2^31: exact int32 arithmetic is the definition and
+ * the int32 output never saturates.  The reference's MovingAverage (average.py:26-33), stepped clock by clock, is
+ * x(t) = s(t-3) + s(t-4) + s(t-5) + s(t-6): taps {0, 0, 0, 1, 1, 1, 1} at shift 0 (its own test expects that timing with
+ * shift 2); software/memdump/adcplot.py:34-36 is taps {1, 1, 1, 1}, decim 4, phase 3. */
+#define BBB_FIR_MAX_TAPS 256
+typedef struct {
+    uint32_t ntaps;       /* 1..256 */
+    int16_t  taps[256];   /* h[0..ntaps-1]; sum |h[i]| <= 65535, else BBB_EINVAL */
+    uint32_t shift;       /* 0..31, arithmetic */
+    uint32_t decim;       /* 1..256: one output per decim inputs */
+    uint32_t phase;       /* < decim: output q sits at input index phase + q * decim */
+    uint32_t out_bytes;   /* 2: int16, saturating.  4: int32 */
+} bbb_fir_cfg;
+
+/* The moving average as a preset (host only, works without a GPU): taps {1, 1, 1, 1}, or with `pipeline` the module's
+ * registers {0, 0, 0, 1, 1, 1, 1}; shift 0, decim 1, phase 0, out_bytes 2. */
+int bbb_fir_moving_average(bbb_fir_cfg *cfg, int pipeline);
+
+/* out_dev[q] = y[q] for q in [0, nout); *nout_out (host, may be NULL) receives nout.  The history convention is
+ * bbb_sinc_interpolate's: in_dev[-1] .. in_dev[-nbefore] must be readable and are the record's earlier samples (only the
+ * nearest ntaps - 1 are used), history beyond them is 0, so a call that is given them continues a stream exactly.  in_dev
+ * may have any 2-byte alignment (an in_dev aligned to 16 bytes takes the wide loads), out_dev any element alignment (an
+ * out_dev aligned to 16 bytes takes the wide stores).  nin = 0 is a no-op.  An out_dev that overlaps the samples read is
+ * BBB_EINVAL, as is everything wrong with cfg, which is checked before the device is touched.  Asynchronous on hip_stream. */
+int bbb_fir_filter(const int16_t *in_dev, uint64_t nin, uint32_t nbefore, const bbb_fir_cfg *cfg, void *out_dev,
+                   uint64_t *nout_out, int device, void *hip_stream);
+
+/* The receiver of rx.py:24-26 (MovingAverage, then `avg.x > 0`) without the filtered samples ever reaching memory:
+ * bit q = acc(phase + q * decim) >= threshold (> threshold with strict != 0), threshold in units of acc; packed LSB first
+ * into u64 words, the layout bbb_rx_slice writes, the unused bits of the last word 0.  cfg->shift and cfg->out_bytes are
+ * ignored.  bits_packed_dev needs ceil(nbits / 64) words; *nbits_out (host, may be NULL) receives nbits = nout. */
+int bbb_fir_slice(const int16_t *in_dev, uint64_t nin, uint32_t nbefore, const bbb_fir_cfg *cfg, int32_t threshold,
+                  int strict, uint64_t *bits_packed_dev, uint64_t *nbits_out, int device, void *hip_stream);
+
 /* ---- GF(2) helpers (host only; the pieces of software/rnghunt this path leans on) ------------ */
 
 /* Berlekamp-Massey (software/rnghunt/src/berlekamp_massey.rs:5-31): minimal polynomial of the bit
