@@ -1,6 +1,6 @@
 """basebandboard_amd -- MI355X (gfx950) implementation of basebandboard's AWGN / PRBS Monte-Carlo
 path: LUTOPT uniform generator, CLT Gaussian generator, PRBS generator / error detector, the
-fused BPSK bit-error trial, and the pulse shaper / transmitter output stream, its eye diagram and bathtub, the BER sweep over its settings, and its autocorrelation and power spectrum; and the
+fused BPSK bit-error trial, and the pulse shaper / transmitter output stream, its eye diagram and bathtub, the BER sweep over its settings (raw or behind a receive filter), and its autocorrelation and power spectrum; and the
 numerically controlled oscillator (gateware/bbb/nco.py) the scope's 16x sinc interpolator (gateware/bbb/sinc.py) and the exact integer FIR filter in front of the receiver's decision (gateware/bbb/average.py).  Compute lives in libbbb_hip.so (C ABI: include/bbb.h); these modules
 mirror the reference's Python interface (gateware/bbb/rng.py, prbs.py, bitshaper.py, tx.py, rx.py).
 """
@@ -16,6 +16,7 @@ from .spectrum import TxAcf, capture_acf, tx_acf, psd, MAX_LAGS  # noqa: F401
 from .nco import NCO, NCOState                           # noqa: F401
 from .sinc import SincInterpolator                       # noqa: F401
 from .fir import FIR, FIRStream                          # noqa: F401
+from .link import LinkSweep                              # noqa: F401
 from .grngstats import (clt_pmf, clt_pmf_delivered, moments, chi_square, tail_table, pdf_cdf, evaluate,  # noqa: F401
                         evaluate_samples)
 from . import gf2, recurrences, grngstats                # noqa: F401

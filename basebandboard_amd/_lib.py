@@ -18,7 +18,7 @@ SYMBOLS = [
     "bbb_lutopt_load_matrix_file", "bbb_lutopt_create", "bbb_lutopt_destroy", "bbb_lutopt_set_stream",
     "bbb_lutopt_is_specialised", "bbb_lutopt_set_staged", "bbb_lutopt_set_custom_fill", "bbb_lutopt_set_custom_ber", "bbb_lutopt_attach_custom_library", "bbb_lutopt_profile", "bbb_lutopt_profile_read", "bbb_lutopt_profile_read_mover", "bbb_lutopt_state_at", "bbb_lutopt_fill_words", "bbb_awgn_fill_i8", "bbb_awgn_fill_i16", "bbb_awgn_prefetch", "bbb_awgn_stream_open", "bbb_awgn_stream_next", "bbb_awgn_stream_read", "bbb_awgn_stream_seek", "bbb_awgn_stream_tell", "bbb_awgn_stream_close", "bbb_awgn_hist",
     "bbb_clt_tree_i16", "bbb_prbs_fill", "bbb_prbs_fill_hint", "bbb_prbs_check", "bbb_prbs_check_dev", "bbb_prbs_state_at",
-    "bbb_prbs_detector_run", "bbb_prbs_detector_stream", "bbb_ber_trials", "bbb_ber_trials_dev", "bbb_ber_run_open", "bbb_ber_run_next", "bbb_ber_run_next_dev", "bbb_ber_run_tell", "bbb_ber_run_close", "bbb_ber_sweep_multi", "bbb_sweep_shard", "bbb_multi_last_info", "bbb_multi_release", "bbb_shaper_fill_i16", "bbb_tx_fill_i16", "bbb_tx_stream_open", "bbb_tx_stream_next", "bbb_tx_stream_read", "bbb_tx_stream_seek", "bbb_tx_stream_tell", "bbb_tx_stream_close", "bbb_rx_slice", "bbb_rx_phase_search", "bbb_eye_accumulate_i16", "bbb_tx_eye_open", "bbb_tx_eye_run", "bbb_tx_eye_close", "bbb_tx_ber_sweep_open", "bbb_tx_ber_sweep_run", "bbb_tx_ber_sweep_close", "bbb_acf_accumulate_i16", "bbb_tx_acf_open", "bbb_tx_acf_run", "bbb_tx_acf_close", "bbb_nco_rom", "bbb_nco_open", "bbb_nco_set_cfg", "bbb_nco_set_stream", "bbb_nco_run", "bbb_nco_get_state", "bbb_nco_set_state", "bbb_nco_close", "bbb_sinc_coefficients", "bbb_sinc_interpolate", "bbb_sinc_eye_open", "bbb_sinc_eye_run", "bbb_sinc_eye_close", "bbb_fir_moving_average", "bbb_fir_filter", "bbb_fir_slice", "bbb_gf2_berlekamp_massey", "bbb_gf2_recur",
+    "bbb_prbs_detector_run", "bbb_prbs_detector_stream", "bbb_ber_trials", "bbb_ber_trials_dev", "bbb_ber_run_open", "bbb_ber_run_next", "bbb_ber_run_next_dev", "bbb_ber_run_tell", "bbb_ber_run_close", "bbb_ber_sweep_multi", "bbb_sweep_shard", "bbb_multi_last_info", "bbb_multi_release", "bbb_shaper_fill_i16", "bbb_tx_fill_i16", "bbb_tx_stream_open", "bbb_tx_stream_next", "bbb_tx_stream_read", "bbb_tx_stream_seek", "bbb_tx_stream_tell", "bbb_tx_stream_close", "bbb_rx_slice", "bbb_rx_phase_search", "bbb_eye_accumulate_i16", "bbb_tx_eye_open", "bbb_tx_eye_run", "bbb_tx_eye_close", "bbb_tx_ber_sweep_open", "bbb_tx_ber_sweep_run", "bbb_tx_ber_sweep_close", "bbb_acf_accumulate_i16", "bbb_tx_acf_open", "bbb_tx_acf_run", "bbb_tx_acf_close", "bbb_nco_rom", "bbb_nco_open", "bbb_nco_set_cfg", "bbb_nco_set_stream", "bbb_nco_run", "bbb_nco_get_state", "bbb_nco_set_state", "bbb_nco_close", "bbb_sinc_coefficients", "bbb_sinc_interpolate", "bbb_sinc_eye_open", "bbb_sinc_eye_run", "bbb_sinc_eye_close", "bbb_fir_moving_average", "bbb_fir_filter", "bbb_fir_slice", "bbb_link_sweep_open", "bbb_link_sweep_run", "bbb_link_sweep_close", "bbb_gf2_berlekamp_massey", "bbb_gf2_recur",
     "bbb_gf2_dot", "bbb_gf2_poly_is_primitive", "bbb_gf2_poly_modexp", "bbb_lutopt_charpoly", "bbb_lutopt_is_full_period",
     "bbb_lutopt_save_matrix_file", "bbb_lutopt_search_candidate", "bbb_lutopt_search",
 ]
@@ -210,6 +210,10 @@ def lib():
     l.bbb_fir_moving_average.argtypes = [C.POINTER(FirCfg), i32]
     l.bbb_fir_filter.argtypes = [vp, u64, C.c_uint32, C.POINTER(FirCfg), vp, u64p, i32, vp]
     l.bbb_fir_slice.argtypes = [vp, u64, C.c_uint32, C.POINTER(FirCfg), C.c_int32, i32, vp, u64p, i32, vp]
+    l.bbb_link_sweep_open.argtypes = [vp, C.POINTER(TxCfg), C.POINTER(TxSetting), i32, C.POINTER(FirCfg), C.c_uint32,
+                                      C.POINTER(EyeCfg), u64, C.POINTER(vp)]
+    l.bbb_link_sweep_run.argtypes = [vp, u64, u64, vp, vp]
+    l.bbb_link_sweep_close.argtypes = [vp]
     u8p = C.POINTER(C.c_uint8)
     l.bbb_gf2_berlekamp_massey.argtypes = [u8p, u64, u8p, C.POINTER(C.c_int64)]
     l.bbb_gf2_recur.argtypes = [i32, i32, u64p, u8p, i32, u8p]

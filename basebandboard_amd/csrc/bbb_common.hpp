@@ -75,6 +75,7 @@ struct EyeLaunch {
 // blocks the accumulate kernel runs with on the current device for launches of up to nsamples (or a negative BBB_E* code),
 // and the u32 words of scratch they need for ncols
 int eye_grid_blocks(uint64_t nsamples);
+int eye_cfg_check(const bbb_eye_cfg *eye);        // eye_api.hip: the rules of bbb_eye_cfg (BBB_EINVAL with a detail)
 inline uint64_t eye_scratch_words(int blocks, uint32_t ncols) { return (uint64_t)blocks * (256u * ncols + 8u); }
 int eye_accumulate_launch(const EyeLaunch &a, const int16_t *samples, uint64_t nsamples, uint64_t first_sample,
                           uint32_t *scratch, int blocks, uint64_t *hist, uint64_t *bathtub, hipStream_t st);
@@ -165,6 +166,38 @@ struct FirLaunch {                                // one launch: any number of i
 };
 // mode 0: int16 out (saturating), 1: int32 out, 2: packed decisions against threshold
 int fir_launch(const FirLaunch &a, int mode, int grid, hipStream_t st);
+// fir_api.hip: the rules of bbb_fir_cfg (BBB_EINVAL with a detail); slice: shift and out_bytes are not looked at
+int fir_cfg_check(const bbb_fir_cfg *c, bool slice);
+
+// link_kernels.hip: eye and bathtub of the shaped link behind a receive filter (include/bbb.h, bbb_link_sweep_*)
+constexpr int kLinkTile = 2048;                   // outputs per workgroup step
+constexpr uint64_t kLinkLaunchMax = 1ull << 31;   // samples per launch
+struct LinkLaunch {                               // one launch: one setting over one chunk; j is a WAVEFORM sample number
+    const int8_t *noise;                          // noise[i] belongs to sample norg + i, i < nnoise; nullptr: the noise is off
+    long long norg;                               // >= 0; tb - norg is a multiple of 8
+    unsigned long long nnoise;                    // a multiple of 8, all readable
+    const unsigned long long *bits;               // data bits from m0 on, nwords u64 words readable; nullptr for the Pulser
+    long long m0;                                 // 0, or at most the lowest bit the launch looks at
+    unsigned long long nwords;
+    int source;                                   // 0 PRBS, 1 Pulser
+    int nv;                                       // noise_var, 0 when the noise is off
+    const uint16_t *table;                        // the setting's shaped values as sweep_tables_launch leaves them
+    long long tb;                                 // sample of the first tile's first output: out_lo - 7 <= tb <= out_lo
+    long long out_lo, out_hi;                     // the outputs that count: stream samples [out_lo - delay, out_hi - delay)
+    uint32_t delay;
+    uint32_t ngroups;                             // groups of four tap words (eight taps) in use: 1..32
+    uint32_t shift;                               // z = sat16(acc >> shift)
+    int32_t threshold;                            // in units of acc
+    int strict;
+    uint32_t ncols, eye_shift;                    // the histogram's bbb_eye_cfg fields
+    uint64_t col_origin;
+    uint32_t taps[BBB_FIR_MAX_TAPS / 2];          // as FirLaunch
+};
+// blocks a launch may use on the current device (or a negative BBB_E* code); its scratch is eye_scratch_words(blocks, ncols)
+int link_grid_blocks(bool hist);
+// counters[8][2] and hist[256][ncols] += what stream samples [first, first + n) of the launch give; either may be nullptr
+int link_launch(const LinkLaunch &a, bool hist, uint64_t first, uint64_t n, uint32_t *scratch, int blocks, uint64_t *hist_out,
+                uint64_t *counters, hipStream_t st);
 
 // bbb_api.hip: what the eye object needs of a handle (reads fields only) and the bbb_tx_cfg checks of bbb_tx_fill_i16
 int lutopt_device(const bbb_lutopt *h);

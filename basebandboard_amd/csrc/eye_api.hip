@@ -16,14 +16,6 @@ constexpr uint64_t kEyeChunkDefault = 1ull << 26;     // 128 MiB of int16: the r
 constexpr uint64_t kEyeChunkMax = 1ull << 30;
 constexpr uint64_t kEyeSampleLimit = 1ull << 62;      // first_sample + nsamples (the transmitter's own range)
 
-int eye_check(const bbb_eye_cfg *eye) {
-    if (!eye) return fail(BBB_EINVAL, "null eye cfg");
-    if (eye->ncols != 8 && eye->ncols != 16 && eye->ncols != 32 && eye->ncols != 64)
-        return fail(BBB_EINVAL, "eye ncols must be 8, 16, 32 or 64 (got " + std::to_string(eye->ncols) + ")");
-    if (eye->shift > 15) return fail(BBB_EINVAL, "eye shift must be 0..15 (got " + std::to_string(eye->shift) + ")");
-    return BBB_OK;
-}
-
 int range_check(uint64_t first, uint64_t n) {
     if (first > kEyeSampleLimit || n > kEyeSampleLimit - first) return fail(BBB_EINVAL, "first_sample + nsamples must be <= 2^62");
     return BBB_OK;
@@ -43,6 +35,14 @@ EyeLaunch launch_of(const bbb_eye_cfg &e) {
 int64_t floor8(int64_t v) { return v >= 0 ? v / 8 : -((-v + 7) / 8); }
 
 }  // namespace
+
+int bbb::eye_cfg_check(const bbb_eye_cfg *eye) {
+    if (!eye) return fail(BBB_EINVAL, "null eye cfg");
+    if (eye->ncols != 8 && eye->ncols != 16 && eye->ncols != 32 && eye->ncols != 64)
+        return fail(BBB_EINVAL, "eye ncols must be 8, 16, 32 or 64 (got " + std::to_string(eye->ncols) + ")");
+    if (eye->shift > 15) return fail(BBB_EINVAL, "eye shift must be 0..15 (got " + std::to_string(eye->shift) + ")");
+    return BBB_OK;
+}
 
 struct bbb_tx_eye {
     bbb_lutopt *h = nullptr;
@@ -67,7 +67,7 @@ extern "C" {
 
 int bbb_eye_accumulate_i16(const int16_t *samples_dev, uint64_t nsamples, uint64_t first_sample, const bbb_eye_cfg *eye,
                            uint64_t *hist_dev, int device, void *hip_stream) {
-    int rc = eye_check(eye);
+    int rc = eye_cfg_check(eye);
     if (rc) return rc;
     if (!hist_dev) return fail(BBB_EINVAL, "null hist_dev: the histogram is the only output of the capture side");
     if (nsamples && !samples_dev) return fail(BBB_EINVAL, "null samples_dev");
@@ -93,7 +93,7 @@ int bbb_tx_eye_open(bbb_lutopt *h, const bbb_tx_cfg *cfg, const bbb_eye_cfg *eye
     if (!out) return fail(BBB_EINVAL, "null out");
     int rc = tx_cfg_check(cfg);
     if (rc) return rc;
-    if ((rc = eye_check(eye))) return rc;
+    if ((rc = eye_cfg_check(eye))) return rc;
     if (chunk_samples > kEyeChunkMax) return fail(BBB_EINVAL, "chunk_samples must be <= 2^30");
     const int device = lutopt_device(h);
     if (device < 0) return fail(BBB_ENODEV, "host-only handle (device -1) cannot generate samples");

@@ -18,24 +18,16 @@
 //    then per block in LDS; the number of bits decided per phase is exact arithmetic on the range, added by the host.
 // Samples per launch are below 2^31 (the host cuts longer ranges), so every u32 count of a block is exact.
 #include "bbb_common.hpp"
+#include "eye_common.hpp"
 
 #include <algorithm>
 
 namespace bbb {
 
 constexpr int kEyeThreads = 1024;
-constexpr int kEyeRows = 256, kEyeLanes = 64;
 constexpr int kEyeUnroll = 4;                          // 16-byte loads in flight per thread
 constexpr uint64_t kEyeLaunchMax = 1ull << 31;         // samples per launch
 typedef uint32_t eye_u32x4 __attribute__((ext_vector_type(4)));
-
-struct EyeTubBits { unsigned long long v[8]; };
-
-__device__ __forceinline__ unsigned eye_row(int x, unsigned shift) {
-    int v = x >> shift;
-    v = v < -128 ? -128 : (v > 127 ? 127 : v);
-    return (unsigned)(127 - v);
-}
 
 __device__ __forceinline__ unsigned eye_decide(int x, int thr, int strict) { return strict ? (x > thr) : (x >= thr); }
 
@@ -160,37 +152,6 @@ eye_accumulate_kernel(EyeLaunch a, const int16_t *__restrict x, unsigned head, u
         }
     }
     if (TUB && threadIdx.x < 8) out[nbins + threadIdx.x] = E[threadIdx.x];
-}
-
-// outputs += the slab: thread t < nbins sums bin t over the blocks, t = nbins + p the errors of phase p
-__global__ void __launch_bounds__(256)
-eye_reduce_kernel(const uint32_t *__restrict scratch, unsigned blocks, unsigned nbins, unsigned long long *__restrict hist,
-                  unsigned long long *__restrict tub, EyeTubBits bits) {
-    const unsigned t = blockIdx.x * 256 + threadIdx.x;
-    if (t >= nbins + 8) return;
-    const bool is_tub = t >= nbins;
-    if (is_tub ? !tub : !hist) return;
-    unsigned long long sum = 0;
-    for (unsigned b = 0; b < blocks; b++) sum += scratch[(unsigned long long)b * (nbins + 8) + t];
-    if (!is_tub) {
-        hist[t] += sum;
-    } else {
-        const unsigned p = t - nbins;
-        tub[2 * p] += bits.v[p];
-        tub[2 * p + 1] += sum;
-    }
-}
-
-// the bits a range of samples decides at each phase: m >= 0 with 8m + 45 + p in [first, first + n)
-static void eye_tub_bits(uint64_t first, uint64_t n, EyeTubBits *b) {
-    const uint64_t last = first + n - 1;
-    for (int p = 0; p < 8; p++) {
-        const uint64_t s = BBB_TX_BIT_SAMPLE0 + p;
-        b->v[p] = 0;
-        if (last < s) continue;
-        const uint64_t lo = first <= s ? 0 : (first - s + 7) / 8, hi = (last - s) / 8;
-        b->v[p] = hi >= lo ? hi - lo + 1 : 0;
-    }
 }
 
 int eye_grid_blocks(uint64_t nsamples) {

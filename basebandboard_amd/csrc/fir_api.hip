@@ -12,20 +12,6 @@ namespace {
 
 constexpr uint64_t kFirSampleLimit = 1ull << 58;
 
-int cfg_check(const bbb_fir_cfg *c, bool slice) {
-    if (!c) return fail(BBB_EINVAL, "null fir cfg");
-    if (c->ntaps < 1 || c->ntaps > BBB_FIR_MAX_TAPS) return fail(BBB_EINVAL, "ntaps must be 1..256 (got " + std::to_string(c->ntaps) + ")");
-    uint32_t sum = 0;
-    for (uint32_t i = 0; i < c->ntaps; ++i) sum += (uint32_t)std::abs((int)c->taps[i]);
-    if (sum > 65535) return fail(BBB_EINVAL, "the sum of |taps| must be <= 65535 (got " + std::to_string(sum) + ")");
-    if (!slice && c->shift > 31) return fail(BBB_EINVAL, "shift must be 0..31 (got " + std::to_string(c->shift) + ")");
-    if (c->decim < 1 || c->decim > 256) return fail(BBB_EINVAL, "decim must be 1..256 (got " + std::to_string(c->decim) + ")");
-    if (c->phase >= c->decim) return fail(BBB_EINVAL, "phase must be < decim (got " + std::to_string(c->phase) + ")");
-    if (!slice && c->out_bytes != 2 && c->out_bytes != 4)
-        return fail(BBB_EINVAL, "out_bytes must be 2 or 4 (got " + std::to_string(c->out_bytes) + ")");
-    return BBB_OK;
-}
-
 bool overlap(const void *a, uint64_t abytes, const void *b, uint64_t bbytes) {
     const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
     return a0 < b0 + bbytes && b0 < a0 + abytes;
@@ -71,6 +57,20 @@ int run(const int16_t *in_dev, uint64_t nin, uint32_t nbefore, const bbb_fir_cfg
 
 }  // namespace
 
+int bbb::fir_cfg_check(const bbb_fir_cfg *c, bool slice) {
+    if (!c) return fail(BBB_EINVAL, "null fir cfg");
+    if (c->ntaps < 1 || c->ntaps > BBB_FIR_MAX_TAPS) return fail(BBB_EINVAL, "ntaps must be 1..256 (got " + std::to_string(c->ntaps) + ")");
+    uint32_t sum = 0;
+    for (uint32_t i = 0; i < c->ntaps; ++i) sum += (uint32_t)std::abs((int)c->taps[i]);
+    if (sum > 65535) return fail(BBB_EINVAL, "the sum of |taps| must be <= 65535 (got " + std::to_string(sum) + ")");
+    if (!slice && c->shift > 31) return fail(BBB_EINVAL, "shift must be 0..31 (got " + std::to_string(c->shift) + ")");
+    if (c->decim < 1 || c->decim > 256) return fail(BBB_EINVAL, "decim must be 1..256 (got " + std::to_string(c->decim) + ")");
+    if (c->phase >= c->decim) return fail(BBB_EINVAL, "phase must be < decim (got " + std::to_string(c->phase) + ")");
+    if (!slice && c->out_bytes != 2 && c->out_bytes != 4)
+        return fail(BBB_EINVAL, "out_bytes must be 2 or 4 (got " + std::to_string(c->out_bytes) + ")");
+    return BBB_OK;
+}
+
 extern "C" {
 
 int bbb_fir_moving_average(bbb_fir_cfg *cfg, int pipeline) {
@@ -86,14 +86,14 @@ int bbb_fir_moving_average(bbb_fir_cfg *cfg, int pipeline) {
 
 int bbb_fir_filter(const int16_t *in_dev, uint64_t nin, uint32_t nbefore, const bbb_fir_cfg *cfg, void *out_dev,
                    uint64_t *nout_out, int device, void *hip_stream) {
-    int rc = cfg_check(cfg, false);
+    int rc = fir_cfg_check(cfg, false);
     if (rc) return rc;
     return run(in_dev, nin, nbefore, cfg, cfg->out_bytes == 4 ? 1 : 0, 0, 0, out_dev, nout_out, device, (hipStream_t)hip_stream);
 }
 
 int bbb_fir_slice(const int16_t *in_dev, uint64_t nin, uint32_t nbefore, const bbb_fir_cfg *cfg, int32_t threshold,
                   int strict, uint64_t *bits_packed_dev, uint64_t *nbits_out, int device, void *hip_stream) {
-    int rc = cfg_check(cfg, true);
+    int rc = fir_cfg_check(cfg, true);
     if (rc) return rc;
     return run(in_dev, nin, nbefore, cfg, 2, threshold, strict, bits_packed_dev, nbits_out, device, (hipStream_t)hip_stream);
 }

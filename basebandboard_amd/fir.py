@@ -61,6 +61,12 @@ class FIR:
     def __len__(self):
         return len(self.taps)
 
+    def delay(self):
+        """The filter's group delay in whole samples: the floor of the centroid of |h| (1 for [1, 1, 1, 1], 4 for the
+        pipelined moving average; 0 for all-zero taps).  What link.LinkSweep re-times the filtered stream by."""
+        total = sum(abs(v) for v in self.taps)
+        return sum(i * abs(v) for i, v in enumerate(self.taps)) // total if total else 0
+
     def _cfg(self, decim, phase, out_bytes=2):
         decim, phase = int(decim), int(phase)
         if not 1 <= decim <= MAX_DECIM:

@@ -50,11 +50,19 @@ class TX:
                        "bbb_awgn_prefetch")
         return out[:nsamples]
 
-    def eye(self, nsamples, first_sample=0, warmup=16, eye=None, chunk_samples=0, hist=None, bathtub=None):
+    def eye(self, nsamples, first_sample=0, warmup=16, eye=None, chunk_samples=0, hist=None, bathtub=None, rx_filter=None,
+            delay=None):
         """Eye histogram and bathtub of `x` over samples [first_sample, first_sample + nsamples), the waveform never
         materialised (bbb_tx_eye_*): (hist [256, ncols] uint64, bathtub [8, 2] uint64 = bits, errors per phase).  `eye`: an
         eye.EyeConfig, default 64 columns, shift 4 and col_origin = eye.BIT_SAMPLE0 (column c is bathtub phase c mod 8).
-        hist / bathtub given: added to."""
+        hist / bathtub given: added to.  rx_filter: a fir.FIR -- eye and bathtub of the stream behind that filter instead,
+        re-timed by `delay` (None: rx_filter.delay()); the histogram bins sat16(acc >> shift), the bathtub decides acc
+        against the eye's threshold in units of acc (bbb_link_sweep_*, link.py)."""
+        if rx_filter is not None:
+            from .link import link_eye
+            return link_eye(self, nsamples, rx_filter, delay, first_sample, warmup, eye, chunk_samples, hist, bathtub)
+        if delay is not None:
+            raise ValueError("delay belongs to rx_filter")
         from .eye import tx_eye
         return tx_eye(self, nsamples, first_sample, warmup, eye, chunk_samples, hist, bathtub)
 
@@ -74,14 +82,16 @@ class TX:
         return psd(tx_acf(self, nsamples, first_sample, nlags, warmup, chunk_samples), int(nsamples), **psd_kw)
 
     def ber_sweep(self, nsamples, noise_vars=range(16), shape_sels=None, threshold=0, strict=False, first_sample=0, warmup=16,
-                  chunk_samples=0, counters=None):
+                  chunk_samples=0, counters=None, rx_filter=None, delay=None):
         """Bathtub of `x` for every (shape_sel, noise_var) of the grid in one pass over the noise stream
         (bbb_tx_ber_sweep_*): [len(shape_sels), len(noise_vars), 8, 2] uint64 = bits, errors per phase, each entry what
         TX.eye's bathtub gives for a TX with that shape_sel and noise_var.  shape_sels None: the TX's own set; bit_en and
-        noise_en are the TX's; the decision x >= threshold (x > threshold when strict).  counters given: added to."""
+        noise_en are the TX's; the decision x >= threshold (x > threshold when strict).  counters given: added to.
+        rx_filter: a fir.FIR -- the bathtub of the stream behind that filter instead, re-timed by `delay` (None:
+        rx_filter.delay()), the threshold then in units of acc (bbb_link_sweep_*, link.py)."""
         from .txsweep import tx_ber_sweep
         return tx_ber_sweep(self, nsamples, noise_vars, shape_sels, threshold, strict, first_sample, warmup, chunk_samples,
-                            counters)
+                            counters, rx_filter, delay)
 
     def stream(self, nsamples_per_call, first_sample=0, warmup=16):
         """TX.x read sequentially (bbb_tx_stream_*): `with tx.stream(n) as s: s.next(out=buf)`."""

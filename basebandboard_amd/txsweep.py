@@ -100,9 +100,16 @@ class TxBerSweep:
 
 
 def tx_ber_sweep(tx, nsamples, noise_vars=range(16), shape_sels=None, threshold=0, strict=False, first_sample=0, warmup=16,
-                 chunk_samples=0, counters=None):
+                 chunk_samples=0, counters=None, rx_filter=None, delay=None):
     """TX.ber_sweep: the bathtub for every (shape_sel, noise_var) of the grid, [len(shape_sels), len(noise_vars), 8, 2]
-    uint64 (bits, errors).  shape_sels None: the TX's own set.  bit_en and noise_en are the TX's."""
+    uint64 (bits, errors).  shape_sels None: the TX's own set.  bit_en and noise_en are the TX's.  rx_filter (a fir.FIR):
+    the bathtub behind that filter, through link.LinkSweep."""
+    if rx_filter is not None:
+        from .link import link_ber_sweep
+        return link_ber_sweep(tx, nsamples, rx_filter, delay, noise_vars, shape_sels, threshold, strict, first_sample, warmup,
+                              chunk_samples, counters)
+    if delay is not None:
+        raise ValueError("delay belongs to rx_filter")
     if shape_sels is None:
         shape_sels = [_shaper(tx).setsel]
     shape_sels, noise_vars = [int(s) for s in shape_sels], [int(v) for v in noise_vars]

@@ -24,6 +24,10 @@
 //                       (bbb_fir_slice with the taps of bbb_fir_moving_average) beside the plain sign slicer (bbb_rx_slice) over a
 //                       noisy transmission of the 4-sample rectangular pulse (the last set of PRBSShaper.from_rcf), each at 8
 //                       samples per bit into the exact detector: one JSON line with both error counts
+//          link:        --link 1 [--eye-samples 1e6] [--prbs 31] [--nv 8] [--shape 16] [--delay 2]   the bathtub of one transmitter
+//                       setting decided on the raw sample (bbb_tx_ber_sweep_*) and behind the moving average of rx.py:24-26
+//                       (bbb_link_sweep_* with the taps of bbb_fir_moving_average, the filtered stream re-timed by `delay`), the
+//                       waveform never materialised: one JSON line per phase with the bits decided and both error counts
 //          spectrum:    --spectrum FILE [--lags 256] [--eye-samples 1e6] [--prbs 31] [--nv 8] [--shape 16]   autocorrelation
 //                       counters of the transmitter's waveform (bbb_tx_acf_*) and the power spectrum from them (Bartlett lag
 //                       window, mean removed, one-sided, fs = 1): FILE gets a CSV k,freq,psd,psd_db (psd_db is nan in a bin
@@ -186,7 +190,7 @@ int main(int argc, char **argv) {
     int lags = 256;
     int shape = 16, eye_shift = 4;
     double eye_samples = 1e6;
-    int tx_sweep = 0, nv_lo = 0, nv_hi = 15, fir = 0;
+    int tx_sweep = 0, nv_lo = 0, nv_hi = 15, fir = 0, link = 0, link_delay = 2;
     unsigned long long init0 = 1;
     double bits = 1e9, from = 0, to = 10, step = 1, loopback = 0, nsamples = 0, grng_eval = 0;
     unsigned long long first_step = 0;
@@ -232,6 +236,8 @@ int main(int argc, char **argv) {
         else if (a == "--shift") eye_shift = std::atoi(v);
         else if (a == "--tx-sweep") tx_sweep = std::atoi(v);
         else if (a == "--fir") fir = std::atoi(v);
+        else if (a == "--link") link = std::atoi(v);
+        else if (a == "--delay") link_delay = std::atoi(v);
         else if (a == "--nv-range") {
             if (std::sscanf(v, "%d:%d", &nv_lo, &nv_hi) != 2) { std::fprintf(stderr, "--nv-range A:B\n"); return 2; }
         }
@@ -623,6 +629,55 @@ int main(int argc, char **argv) {
                     (unsigned long long)nfft, secs, specfile.c_str());
         for (size_t i = 0; i < nw; i++) std::printf("%s%lld", i ? ", " : "", (long long)acf[i]);
         std::printf("]}\n");
+        return 0;
+    }
+
+    // ---- the bathtub of one setting, raw and behind the moving average (bbb_link_sweep_*) ------------------------------------
+    if (link) {
+        if (shape < 0 || shape > 31 || eye_samples < 1 || nv < 0 || nv > 15 || link_delay < 0 || link_delay > 255) {
+            std::fprintf(stderr, "--shape 0..31, --eye-samples >= 1, --nv 0..15, --delay 0..255\n");
+            return 2;
+        }
+        bbb_tx_cfg base{};
+        base.source = 0;
+        base.prbs_k = k;
+        base.prbs_state = 1;
+        base.warmup = 16;
+        bbb_tx_setting st{};
+        rcf_taps(shape == 31 ? 1.0 : shape * (1.0 / 31), st.coeffs);            // tx.py:54: np.linspace(0, 1, 32)
+        st.bit_en = 1;
+        st.noise_en = 1;
+        st.noise_var = nv;
+        const uint64_t init[8] = {init0, 0, 0, 0, 0, 0, 0, 0};
+        bbb_lutopt *h = nullptr;
+        CHECK(bbb_lutopt_create(&h, m.n, m.taps.data(), m.off.data(), init, 0));
+        bbb_tx_ber_sweep *raw = nullptr;
+        CHECK(bbb_tx_ber_sweep_open(h, &base, &st, 1, 0, &raw));
+        bbb_fir_cfg fc;
+        CHECK(bbb_fir_moving_average(&fc, 0));
+        bbb_link_sweep *ma = nullptr;
+        CHECK(bbb_link_sweep_open(h, &base, &st, 1, &fc, (uint32_t)link_delay, nullptr, 0, &ma));
+        uint64_t *d = nullptr;
+        if (hipMalloc((void **)&d, 32 * sizeof(uint64_t)) != hipSuccess || hipMemset(d, 0, 32 * sizeof(uint64_t)) != hipSuccess) {
+            std::fprintf(stderr, "hipMalloc failed\n");
+            return 1;
+        }
+        const double t0 = now_s();
+        CHECK(bbb_tx_ber_sweep_run(raw, 0, (uint64_t)eye_samples, d));
+        CHECK(bbb_link_sweep_run(ma, 0, (uint64_t)eye_samples, d + 16, nullptr));
+        uint64_t out[32];
+        if (hipMemcpy(out, d, sizeof out, hipMemcpyDeviceToHost) != hipSuccess) { std::fprintf(stderr, "hipMemcpy failed\n"); return 1; }
+        const double secs = now_s() - t0;
+        CHECK(bbb_link_sweep_close(ma));
+        CHECK(bbb_tx_ber_sweep_close(raw));
+        CHECK(bbb_lutopt_destroy(h));
+        (void)hipFree(d);
+        std::printf("{\"mode\": \"link\", \"samples\": %llu, \"prbs\": %d, \"shape\": %d, \"nv\": %d, \"taps\": [1, 1, 1, 1], \"delay\": %d, "
+                    "\"seconds\": %.4f}\n", (unsigned long long)eye_samples, k, shape, nv, link_delay, secs);
+        for (int p = 0; p < 8; p++)
+            std::printf("{\"phase\": %d, \"bits\": %llu, \"raw_errors\": %llu, \"filtered_bits\": %llu, \"filtered_errors\": %llu}\n", p,
+                        (unsigned long long)out[2 * p], (unsigned long long)out[2 * p + 1], (unsigned long long)out[16 + 2 * p],
+                        (unsigned long long)out[16 + 2 * p + 1]);
         return 0;
     }
 

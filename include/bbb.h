@@ -646,6 +646,38 @@ int bbb_fir_filter(const int16_t *in_dev, uint64_t nin, uint32_t nbefore, const 
 int bbb_fir_slice(const int16_t *in_dev, uint64_t nin, uint32_t nbefore, const bbb_fir_cfg *cfg, int32_t threshold,
                   int strict, uint64_t *bits_packed_dev, uint64_t *nbits_out, int device, void *hip_stream);
 
+/* ---- the filtered link: eye, bathtub and BER sweep behind a receive filter (rx.py:24-26) -------------------------------- */
+
+/* What bbb_tx_eye_run and bbb_tx_ber_sweep_run give for the raw sample, for the sample AFTER the receive filter, the
+ * waveform and the filtered stream never reaching memory.  With x(n) = bbb_tx_fill_i16 of *base with settings[i]'s coeffs,
+ * bit_en, noise_en and noise_var (x(n) = 0 for n < 0):
+ *   acc(n) = sum_{i < ntaps} h[i] * x(n - i)     exact int32, the rules of bbb_fir_cfg
+ *   z(n)   = sat16(acc(n) >> fir->shift)
+ * and the filtered stream re-timed by `delay` (0..255, the filter's group delay): stream sample n is acc(n + delay) /
+ * z(n + delay).  counters_dev[i][p] ([nset][8][2] uint64, ADDED TO) is the bathtub of that stream: phase p decides data bit
+ * m from stream sample 8m + BBB_TX_BIT_SAMPLE0 + p as acc >= settings[i].threshold (> with strict), the threshold in units
+ * of acc as in bbb_fir_slice; only bits m >= 0 whose stream sample lies in the range count.  hist_dev[i] ([nset][256][ncols]
+ * uint64, ADDED TO; only when *eye was given at open) is bbb_eye_accumulate_i16 of the values z at their stream sample
+ * numbers: eye->ncols, shift and col_origin are used, its threshold and strict are not (each setting carries its own).
+ * run covers stream samples [first_sample, first_sample + nsamples); the filter's history in front of first_sample is the
+ * true waveform, so the totals do not depend on how a range is cut into calls or chunks.  counters_dev may be NULL when a
+ * histogram is filled.  So for taps {1}, shift 0, delay 0 the counters are bbb_tx_ber_sweep_run's and the histogram is
+ * bbb_tx_eye_run's; in general a phase's counters are those of bbb_fir_slice at stride 8 on bbb_tx_fill_i16's output.
+ * fir->decim must be 1 and fir->phase 0 (BBB_EINVAL otherwise); fir->out_bytes is ignored.  nset is 1..512; every setting is
+ * checked as bbb_tx_ber_sweep_open checks it, and every argument before the device is touched.  The noise of a chunk
+ * (chunk_samples, 0: 2^26) is generated once, with the filter's history and `delay` samples of overlap between chunks, the
+ * data bits once; one launch per setting re-reads them from the cache.  Handles that bbb_tx_fill_i16 refuses with noise on
+ * get the same BBB_EUNSUP from run when a setting has noise_en.  Asynchronous on the handle's stream; the handle's own stream
+ * position is left as it was.  LIFETIME: as bbb_tx_ber_sweep -- close the object BEFORE bbb_lutopt_destroy of its handle. */
+typedef struct bbb_link_sweep bbb_link_sweep;
+int bbb_link_sweep_open(bbb_lutopt *h, const bbb_tx_cfg *base, const bbb_tx_setting *settings, int nset, const bbb_fir_cfg *fir,
+                        uint32_t delay, const bbb_eye_cfg *eye /* NULL: no histograms */, uint64_t chunk_samples,
+                        bbb_link_sweep **out);
+int bbb_link_sweep_run(bbb_link_sweep *s, uint64_t first_sample, uint64_t nsamples,
+                       uint64_t *counters_dev /* [nset][8][2], added to, may be NULL if hist_dev is not */,
+                       uint64_t *hist_dev /* [nset][256][ncols], added to, NULL or eye was NULL: none */);
+int bbb_link_sweep_close(bbb_link_sweep *s);
+
 /* ---- GF(2) helpers (host only; the pieces of software/rnghunt this path leans on) ------------ */
 
 /* Berlekamp-Massey (software/rnghunt/src/berlekamp_massey.rs:5-31): minimal polynomial of the bit
