@@ -34,6 +34,16 @@ int use_device(int device);
 
 constexpr int kWave = 64;   // CDNA wavefront
 
+// floor(v / 8) for signed v
+inline int64_t floor8(int64_t v) { return v >= 0 ? v / 8 : -((-v + 7) / 8); }
+
+// the transmitter's own range, for every call that takes first_sample and nsamples
+inline int tx_range_check(uint64_t first, uint64_t n) {
+    constexpr uint64_t limit = 1ull << 62;
+    if (first > limit || n > limit - first) return fail(BBB_EINVAL, "first_sample + nsamples must be <= 2^62");
+    return BBB_OK;
+}
+
 // Timing-experiment knobs (kernel variants selected through the environment) exist only in builds made with
 // -DBBB_EXPERIMENTS; the shipped library ignores the environment: no variable can change what it computes.
 #ifdef BBB_EXPERIMENTS

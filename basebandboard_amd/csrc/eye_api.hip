@@ -14,12 +14,6 @@ namespace {
 
 constexpr uint64_t kEyeChunkDefault = 1ull << 26;     // 128 MiB of int16: the reader finds the chunk in the Infinity Cache
 constexpr uint64_t kEyeChunkMax = 1ull << 30;
-constexpr uint64_t kEyeSampleLimit = 1ull << 62;      // first_sample + nsamples (the transmitter's own range)
-
-int range_check(uint64_t first, uint64_t n) {
-    if (first > kEyeSampleLimit || n > kEyeSampleLimit - first) return fail(BBB_EINVAL, "first_sample + nsamples must be <= 2^62");
-    return BBB_OK;
-}
 
 EyeLaunch launch_of(const bbb_eye_cfg &e) {
     EyeLaunch a{};
@@ -30,9 +24,6 @@ EyeLaunch launch_of(const bbb_eye_cfg &e) {
     a.strict = e.strict != 0;
     return a;
 }
-
-// floor(v / 8) for signed v
-int64_t floor8(int64_t v) { return v >= 0 ? v / 8 : -((-v + 7) / 8); }
 
 }  // namespace
 
@@ -72,7 +63,7 @@ int bbb_eye_accumulate_i16(const int16_t *samples_dev, uint64_t nsamples, uint64
     if (!hist_dev) return fail(BBB_EINVAL, "null hist_dev: the histogram is the only output of the capture side");
     if (nsamples && !samples_dev) return fail(BBB_EINVAL, "null samples_dev");
     if (((uintptr_t)samples_dev & 1) || ((uintptr_t)hist_dev & 7)) return fail(BBB_EINVAL, "misaligned device pointer");
-    if ((rc = range_check(first_sample, nsamples))) return rc;
+    if ((rc = tx_range_check(first_sample, nsamples))) return rc;
     if (nsamples == 0) return BBB_OK;
     if ((rc = use_device(device))) return rc;
     hipStream_t st = (hipStream_t)hip_stream;
@@ -119,7 +110,7 @@ int bbb_tx_eye_run(bbb_tx_eye *e, uint64_t first_sample, uint64_t nsamples, uint
     if (!hist_dev && !bathtub_dev) return fail(BBB_EINVAL, "hist_dev and bathtub_dev are both NULL");
     if (!e) return fail(BBB_EINVAL, "null eye object");
     if (((uintptr_t)hist_dev & 7) || ((uintptr_t)bathtub_dev & 7)) return fail(BBB_EINVAL, "misaligned device pointer");
-    int rc = range_check(first_sample, nsamples);
+    int rc = tx_range_check(first_sample, nsamples);
     if (rc) return rc;
     if (nsamples == 0) return BBB_OK;
     BBB_HIP(hipSetDevice(e->device));

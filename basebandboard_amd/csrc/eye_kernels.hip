@@ -3,19 +3,17 @@
 // Reference semantics: the DSO of gateware/bbb/dso.py:12-72 (256 rows x 64 columns, row = 127 - sample, column = position
 // after a line trigger), counted instead of lit; the bathtub decides data bit m from sample 8m + 45 + p at phase p.
 //
-// One accumulate kernel serves the capture side (bbb_eye_accumulate_i16) and the transmitter side (bbb_tx_eye_run):
-//  - every block keeps its histogram in LDS as u32 counts laid out [256 rows][64 LANE-COLUMNS]: lane-column lc holds the
-//    samples with (n - col_origin) mod 64 = lc and is folded to column lc mod ncols at the flush.  The bank of a b32 LDS
-//    access is (a/4) mod 32 in lane groups of 32 (MI355X_MICROARCH.md, LDS), and row * 64 is a multiple of 32, so an
-//    instruction whose 32 lanes touch 32 distinct lane-columns mod 32 is free of conflicts whatever the rows are;
-//  - a thread reads 8 consecutive samples with one 16-byte load (group g of the body, g = lane mod 8 within 8 lanes), so at
-//    step j lanes l, l+4, ..., l+28 would all sit on lane-column cb + 8 (l mod 4) + j mod 32: eight lanes on one bank.  Each
-//    lane instead takes its 8 samples ROTATED by t = (l >> 2) & 7 (three select stages): at step j lane l adds sample
-//    (j + t) mod 8, and the 32 lanes of a group cover 32 distinct banks;
-//  - the flush writes the block's folded partial with plain stores to a scratch slab ([blocks][256 ncols + 8] u32); a small
-//    reduce kernel adds the slab into the u64 outputs (no global atomics: 256 blocks x 16 Ki bins would be 4 M of them);
+// One accumulate kernel serves the capture side (bbb_eye_accumulate_i16) and the transmitter side (bbb_tx_eye_run).  What a
+// block keeps and how it hands it on is eye_common.hpp's, shared with the filtered link (link_kernels.hip):
+//  - the histogram in LDS, [256 rows][64 lane-columns] u32, folded to ncols at the flush.  A thread reads 8 consecutive
+//    samples with one 16-byte load (group g of the body, g = lane mod 8 within 8 lanes) and adds them with eye_add8, whose
+//    rotation keeps the 32 lanes of a group on 32 distinct banks;
+//  - the flush (eye_flush) writes the block's folded partial with plain stores to a scratch slab ([blocks][256 ncols + 8]
+//    u32); eye_reduce_launch adds the slab into the u64 outputs (no global atomics: 256 blocks x 16 Ki bins would be 4 M of
+//    them);
 //  - bathtub errors are counted in registers per sample slot j (slot j of every group has the same phase), reduced per wave,
-//    then per block in LDS; the number of bits decided per phase is exact arithmetic on the range, added by the host.
+//    then per block in LDS (eye_fold_errors); the number of bits decided per phase is exact arithmetic on the range, added by
+//    the host.
 // Samples per launch are below 2^31 (the host cuts longer ranges), so every u32 count of a block is exact.
 #include "bbb_common.hpp"
 #include "eye_common.hpp"
@@ -27,9 +25,6 @@ namespace bbb {
 constexpr int kEyeThreads = 1024;
 constexpr int kEyeUnroll = 4;                          // 16-byte loads in flight per thread
 constexpr uint64_t kEyeLaunchMax = 1ull << 31;         // samples per launch
-typedef uint32_t eye_u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ unsigned eye_decide(int x, int thr, int strict) { return strict ? (x > thr) : (x >= thr); }
 
 // data bit m, or -1 when it does not count (m < 0, or outside the bits supplied)
 __device__ __forceinline__ int eye_bit(const EyeLaunch &a, long long m) {
@@ -49,11 +44,7 @@ eye_accumulate_kernel(EyeLaunch a, const int16_t *__restrict x, unsigned head, u
                       unsigned long long first, uint32_t *__restrict scratch) {
     __shared__ uint32_t H[HIST ? kEyeRows * kEyeLanes : 1];
     __shared__ uint32_t E[8];
-    if constexpr (HIST) {
-        eye_u32x4 *h4 = reinterpret_cast<eye_u32x4 *>(H);
-        for (int i = threadIdx.x; i < kEyeRows * kEyeLanes / 4; i += kEyeThreads) h4[i] = eye_u32x4{0u, 0u, 0u, 0u};
-    }
-    if (threadIdx.x < 8) E[threadIdx.x] = 0;
+    eye_zero<HIST>(H, E, threadIdx.x, kEyeThreads);
     __syncthreads();
 
     const unsigned lane = threadIdx.x & 63;
@@ -97,17 +88,7 @@ eye_accumulate_kernel(EyeLaunch a, const int16_t *__restrict x, unsigned head, u
                 unsigned A[8];
 #pragma unroll
                 for (int r = 0; r < 8; r++) A[r] = eye_row(s[r], a.shift) * kEyeLanes + ((cb + r) & 63);
-#pragma unroll
-                for (unsigned sh = 1; sh < 8; sh <<= 1) {                    // A[j] <- A[(j + rot) mod 8]
-                    const bool on = rot & sh;
-                    unsigned B[8];
-#pragma unroll
-                    for (int j = 0; j < 8; j++) B[j] = on ? A[(j + sh) & 7] : A[j];
-#pragma unroll
-                    for (int j = 0; j < 8; j++) A[j] = B[j];
-                }
-#pragma unroll
-                for (int j = 0; j < 8; j++) atomicAdd(&H[A[j]], 1u);
+                eye_add8<false>(H, A, rot);
             }
         }
     }
@@ -128,30 +109,9 @@ eye_accumulate_kernel(EyeLaunch a, const int16_t *__restrict x, unsigned head, u
             }
         }
     }
-    if constexpr (TUB) {
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            uint32_t e = err[j];
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) e += __shfl_xor(e, o);
-            if (lane == 0 && e) atomicAdd(&E[(d + j) & 7], e);
-        }
-    }
+    if constexpr (TUB) eye_fold_errors(E, err, d, lane);
     __syncthreads();
-
-    // flush: fold the 64 lane-columns to ncols and store the block's partial
-    const unsigned nbins = kEyeRows * a.ncols;
-    uint32_t *out = scratch + (unsigned long long)blockIdx.x * (nbins + 8);
-    if constexpr (HIST) {
-        const unsigned lg = 31 - __builtin_clz(a.ncols), fold = kEyeLanes >> lg;
-        for (unsigned bin = threadIdx.x; bin < nbins; bin += kEyeThreads) {
-            const unsigned row = bin >> lg, col = bin & (a.ncols - 1);
-            uint32_t sum = 0;
-            for (unsigned k = 0; k < fold; k++) sum += H[row * kEyeLanes + col + (k << lg)];
-            out[bin] = sum;
-        }
-    }
-    if (TUB && threadIdx.x < 8) out[nbins + threadIdx.x] = E[threadIdx.x];
+    eye_flush<HIST, TUB>(H, E, scratch, kEyeRows * a.ncols, a.ncols, threadIdx.x, kEyeThreads);
 }
 
 int eye_grid_blocks(uint64_t nsamples) {
@@ -182,11 +142,8 @@ int eye_accumulate_launch(const EyeLaunch &a, const int16_t *samples, uint64_t n
         else
             eye_accumulate_kernel<false, true><<<nb, kEyeThreads, 0, st>>>(a, x, head, ngroups, n, first, scratch);
         BBB_HIP(hipGetLastError());
-        EyeTubBits tb;
-        eye_tub_bits(first, n, &tb);
-        eye_reduce_kernel<<<(nbins + 8 + 255) / 256, 256, 0, st>>>(scratch, nb, nbins, reinterpret_cast<unsigned long long *>(a.want_hist ? hist : nullptr),
-                                                                   reinterpret_cast<unsigned long long *>(a.want_tub ? bathtub : nullptr), tb);
-        BBB_HIP(hipGetLastError());
+        const int rc = eye_reduce_launch(scratch, nb, nbins, a.want_hist ? hist : nullptr, a.want_tub ? bathtub : nullptr, first, n, st);
+        if (rc) return rc;
         off += n;
     }
     return BBB_OK;

@@ -8,32 +8,21 @@
 // as sinc_kernel does (16-byte loads where the input is 16-byte aligned and the chunk lies inside the record, 2-byte loads
 // otherwise); the two LDS buffers alternate, so a step costs one barrier.
 //
-// fir_block_kernel (decim = 1): a thread produces the 8 outputs n0 .. n0 + 7, n0 = 8 t.  The pairs of its odd outputs are
-// aligned dwords, those of its even outputs straddle two and are made with v_alignbyte_b32.  Going from pair p to p + 1
-// moves every window down by exactly one dword, so four pairs cost one 16-byte LDS read (aligned: 4 t + 128 - 4 g),
-// four new v_alignbyte_b32 and 32 dot products.
-// fir_point_kernel (decim > 1): a thread produces one requested output at a time; per pair one ds_read_b32, one
+// The image and the block core are fir_common.hpp's, shared with the filtered link (link_kernels.hip).
+// Block form (decim = 1): a thread produces the 8 outputs n0 .. n0 + 7, n0 = 8 t, with fir_block8.
+// Point form (decim > 1): a thread produces one requested output at a time; per pair one ds_read_b32, one
 // v_alignbyte_b32 whose byte selector (0 or 2) is the lane's parity, and one dot product.
 // The slicer writes no samples: the block kernel's 8 decisions are one byte of the packed output, the point kernel takes a
 // ballot of 64 consecutive bits (lane = q mod 64) and stores whole words, or ORs the words a step shares with its neighbour
 // into the zeroed output.
 #include "bbb_common.hpp"
+#include "eye_common.hpp"
+#include "fir_common.hpp"
 
 #include <algorithm>
 
 namespace bbb {
 namespace {
-
-constexpr int kThreads = 256;
-constexpr int kTile = kFirTile;               // inputs per workgroup step: 8 per thread
-constexpr int kHist = 256;                    // LDS samples in front of a step's first input (8 * ngroups are staged)
-constexpr int kLdsWords = (kHist + kTile) / 2 + 4;
-
-typedef short v2s __attribute__((ext_vector_type(2)));
-
-__device__ inline int dot2(uint32_t x, uint32_t h, int acc) {
-    return __builtin_amdgcn_sdot2(__builtin_bit_cast(v2s, x), __builtin_bit_cast(v2s, h), acc, false);
-}
 
 // the samples j0 .. j0 + 7 as four dwords; 0 before in[-nbefore] and from in[nin] on
 __device__ inline uint4 load8(const FirLaunch &a, int64_t j0) {
@@ -51,19 +40,15 @@ __device__ inline uint4 load8(const FirLaunch &a, int64_t j0) {
     return make_uint4(w[0], w[1], w[2], w[3]);
 }
 
-__device__ inline bool decide(const FirLaunch &a, int acc) { return a.strict ? acc > a.threshold : acc >= a.threshold; }
-
-__device__ inline int sat16(int v) { return min(max(v, -32768), 32767); }
-
 // MODE 0: int16 out, 1: int32 out, 2: packed decisions.  POINT: the kernel for decim > 1.
 template <int MODE, bool POINT>
-__global__ __launch_bounds__(kThreads) void fir_kernel(FirLaunch a) {
-    __shared__ __attribute__((aligned(16))) uint32_t lds[2][kLdsWords];
+__global__ __launch_bounds__(kFirThreads) void fir_kernel(FirLaunch a) {
+    __shared__ __attribute__((aligned(16))) uint32_t lds[2][kFirLdsWords];
     const int t = threadIdx.x;
-    const uint64_t nsteps = (a.nin + kTile - 1) / kTile;
+    const uint64_t nsteps = (a.nin + kFirTile - 1) / kFirTile;
     const int ng = (int)a.ngroups;
-    auto own = [&](uint64_t step) { return load8(a, (int64_t)(step * kTile) + 8 * t); };
-    auto lead = [&](uint64_t step) { return t < ng ? load8(a, (int64_t)(step * kTile) - 8 * (t + 1)) : make_uint4(0, 0, 0, 0); };
+    auto own = [&](uint64_t step) { return load8(a, (int64_t)(step * kFirTile) + 8 * t); };
+    auto lead = [&](uint64_t step) { return t < ng ? load8(a, (int64_t)(step * kFirTile) - 8 * (t + 1)) : make_uint4(0, 0, 0, 0); };
     uint64_t s = blockIdx.x;
     uint4 cur = make_uint4(0, 0, 0, 0), cur_lead = cur;
     if (s < nsteps) {
@@ -71,15 +56,15 @@ __global__ __launch_bounds__(kThreads) void fir_kernel(FirLaunch a) {
         cur_lead = lead(s);
     }
     for (int par = 0; s < nsteps; s += gridDim.x, par ^= 1) {
-        const uint64_t base = s * kTile, next = s + gridDim.x;
+        const uint64_t base = s * kFirTile, next = s + gridDim.x;
         uint4 nxt = make_uint4(0, 0, 0, 0), nxt_lead = nxt;
         if (next < nsteps) {
             nxt = own(next);
             nxt_lead = lead(next);
         }
         uint32_t *L = lds[par];
-        *reinterpret_cast<uint4 *>(L + kHist / 2 + 4 * t) = cur;
-        if (t < ng) *reinterpret_cast<uint4 *>(L + kHist / 2 - 4 * (t + 1)) = cur_lead;
+        *reinterpret_cast<uint4 *>(L + kFirHist / 2 + 4 * t) = cur;
+        if (t < ng) *reinterpret_cast<uint4 *>(L + kFirHist / 2 - 4 * (t + 1)) = cur_lead;
         cur = nxt;
         cur_lead = nxt_lead;
         __syncthreads();
@@ -87,38 +72,13 @@ __global__ __launch_bounds__(kThreads) void fir_kernel(FirLaunch a) {
             const uint64_t n0 = base + 8 * t;
             // the slicer also writes the zero bytes that complete the last word
             if (n0 >= (MODE == 2 ? (a.nin + 63) / 64 * 64 : a.nin)) continue;
-            const int D0 = kHist / 2 + 4 * t;                       // the dword of x[n0], x[n0 + 1]
-            uint4 h4 = *reinterpret_cast<const uint4 *>(L + D0);
-            uint32_t d[8], al[7];
-            d[4] = h4.x, d[5] = h4.y, d[6] = h4.z, d[7] = h4.w;
-#pragma unroll
-            for (int k = 4; k < 7; ++k) al[k] = __builtin_amdgcn_alignbyte(d[k + 1], d[k], 2);
-            int acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            for (int g = 0; g < ng; ++g) {
-                // d[k] is dword D0 - 4 g - 4 + k, al[k] its high sample with the low sample of the next
-                const uint4 l4 = *reinterpret_cast<const uint4 *>(L + D0 - 4 * (g + 1));
-                d[0] = l4.x, d[1] = l4.y, d[2] = l4.z, d[3] = l4.w;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) al[k] = __builtin_amdgcn_alignbyte(d[k + 1], d[k], 2);
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const uint32_t h = a.taps[4 * g + u];
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        acc[2 * r + 1] = dot2(d[4 - u + r], h, acc[2 * r + 1]);
-                        acc[2 * r] = dot2(al[3 - u + r], h, acc[2 * r]);
-                    }
-                }
-#pragma unroll
-                for (int k = 0; k < 4; ++k) d[4 + k] = d[k];
-#pragma unroll
-                for (int k = 0; k < 3; ++k) al[4 + k] = al[k];
-            }
+            int acc[8];
+            fir_block8(L, t, ng, a.taps, acc);
             const int nv = (int)min((uint64_t)8, a.nin > n0 ? a.nin - n0 : 0);     // outputs of this thread inside the record
             if constexpr (MODE == 2) {
                 uint32_t byte = 0;
 #pragma unroll
-                for (int r = 0; r < 8; ++r) byte |= (uint32_t)(r < nv && decide(a, acc[r])) << r;
+                for (int r = 0; r < 8; ++r) byte |= (uint32_t)(r < nv && eye_decide(acc[r], a.threshold, a.strict)) << r;
                 reinterpret_cast<uint8_t *>(a.out)[n0 >> 3] = (uint8_t)byte;
             } else if constexpr (MODE == 0) {
                 int16_t *out = reinterpret_cast<int16_t *>(a.out) + n0;
@@ -148,16 +108,16 @@ __global__ __launch_bounds__(kThreads) void fir_kernel(FirLaunch a) {
             }
         } else {
             // the outputs whose input index lies in this step: q_lo <= q < q_hi
-            const uint64_t end = base + kTile;
+            const uint64_t end = base + kFirTile;
             const uint64_t q_lo = base <= a.phase ? 0 : (base - a.phase + a.decim - 1) / a.decim;
             const uint64_t q_hi = end <= a.phase ? 0 : min(a.nout, (end - a.phase + a.decim - 1) / a.decim);
             const int lane = t & 63;
-            for (uint64_t qb = (q_lo & ~63ull) + (uint64_t)(t - lane); qb < q_hi; qb += kThreads) {
+            for (uint64_t qb = (q_lo & ~63ull) + (uint64_t)(t - lane); qb < q_hi; qb += kFirThreads) {
                 const uint64_t q = qb + lane;
                 const bool valid = q >= q_lo && q < q_hi;
                 int acc = 0;
                 if (valid) {
-                    const int l0 = (int)(a.phase + q * a.decim - base) + kHist - 1;     // the lower sample of pair 0
+                    const int l0 = (int)(a.phase + q * a.decim - base) + kFirHist - 1;     // the lower sample of pair 0
                     const int dw = l0 >> 1;
                     const uint32_t sel = (l0 & 1) ? 2u : 0u;
                     uint32_t prev = L[dw + 1];
@@ -171,7 +131,7 @@ __global__ __launch_bounds__(kThreads) void fir_kernel(FirLaunch a) {
                     }
                 }
                 if constexpr (MODE == 2) {
-                    const unsigned long long bits = __ballot(valid && decide(a, acc)), mask = __ballot(valid);
+                    const unsigned long long bits = __ballot(valid && eye_decide(acc, a.threshold, a.strict)), mask = __ballot(valid);
                     if (lane == 0 && mask) {
                         unsigned long long *w = reinterpret_cast<unsigned long long *>(a.out) + (qb >> 6);
                         if (mask == ~0ull) *w = bits;
@@ -189,14 +149,14 @@ __global__ __launch_bounds__(kThreads) void fir_kernel(FirLaunch a) {
 
 template <int MODE>
 void launch_mode(const FirLaunch &a, unsigned g, hipStream_t st) {
-    if (a.decim == 1) fir_kernel<MODE, false><<<g, kThreads, 0, st>>>(a);
-    else fir_kernel<MODE, true><<<g, kThreads, 0, st>>>(a);
+    if (a.decim == 1) fir_kernel<MODE, false><<<g, kFirThreads, 0, st>>>(a);
+    else fir_kernel<MODE, true><<<g, kFirThreads, 0, st>>>(a);
 }
 
 }  // namespace
 
 int fir_launch(const FirLaunch &a, int mode, int grid, hipStream_t st) {
-    const uint64_t nsteps = (a.nin + kTile - 1) / kTile;
+    const uint64_t nsteps = (a.nin + kFirTile - 1) / kFirTile;
     const unsigned g = (unsigned)std::min<uint64_t>(nsteps, (uint64_t)grid);
     if (mode == 0) launch_mode<0>(a, g, st);
     else if (mode == 1) launch_mode<1>(a, g, st);

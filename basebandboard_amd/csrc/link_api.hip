@@ -18,12 +18,8 @@ namespace {
 
 constexpr uint64_t kLinkChunkDefault = 1ull << 26;    // 64 MiB of int8 noise: every launch of a chunk finds it in the Infinity Cache
 constexpr uint64_t kLinkChunkMax = 1ull << 30;
-constexpr uint64_t kLinkSampleLimit = 1ull << 62;     // first_sample + nsamples (the transmitter's own range)
 constexpr int kLinkMaxSettings = 512;
 constexpr uint32_t kLinkMaxDelay = 255;
-
-// floor(v / 8) for signed v
-int64_t floor8(int64_t v) { return v >= 0 ? v / 8 : -((-v + 7) / 8); }
 
 struct LinkSetting {
     int table;                    // index into the object's tables
@@ -154,8 +150,7 @@ int bbb_link_sweep_run(bbb_link_sweep *s, uint64_t first_sample, uint64_t nsampl
     uint64_t *hist = s->have_eye ? hist_dev : nullptr;
     if (!counters_dev && !hist) return fail(BBB_EINVAL, "counters_dev is NULL and there is no histogram to fill");
     if (((uintptr_t)counters_dev & 7) || ((uintptr_t)hist_dev & 7)) return fail(BBB_EINVAL, "misaligned device pointer");
-    if (first_sample > kLinkSampleLimit || nsamples > kLinkSampleLimit - first_sample)
-        return fail(BBB_EINVAL, "first_sample + nsamples must be <= 2^62");
+    if (const int rc = tx_range_check(first_sample, nsamples)) return rc;
     if (nsamples == 0) return BBB_OK;
     if (s->any_noise && s->base.warmup + first_sample + nsamples + s->delay < nsamples + s->delay)
         return fail(BBB_EINVAL, "warmup + first_sample + nsamples overflows");

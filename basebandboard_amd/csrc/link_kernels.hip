@@ -12,17 +12,17 @@
 //     when it is copied in); threads t < ngroups also form the 8 ngroups samples in front of the tile.  The host places the
 //     tiles so that j0 - norg (norg: the sample of noise[0]) is a multiple of 8 and (j0 - 17) mod 8 is one value c0 for the
 //     whole launch;
-//  2. the image is fir_kernel's: the block form runs on it unchanged (sliding 16-byte LDS window, v_dot2_i32_i16 against tap
-//     words read with scalar loads, eight outputs per thread).  Two images alternate, so a step costs one barrier;
+//  2. the image is fir_common.hpp's, and fir_block8, the one block core fir_kernel runs too, gives every thread its eight
+//     outputs from it.  Two images alternate, so a step costs one barrier;
 //  3. slot r of every thread has the same bathtub phase: the errors are counted in 8 registers, and the two data bits a
 //     thread's outputs belong to sit in the window it formed its samples from;
-//  4. HIST: the eye kernel's LDS histogram, [256 rows][64 lane-columns] u32 with the rotation that keeps a wave's 32 lanes on
-//     32 banks, folded to ncols at the flush.
-// The block's partial goes to a scratch slab with plain stores and eye_reduce_kernel folds it in u64 (no global atomics);
+//  4. HIST: eye_common.hpp's LDS histogram (eye_add8 with its mask for the outputs that do not count, eye_flush).
+// The block's partial goes to a scratch slab with plain stores and eye_reduce_launch folds it in u64 (no global atomics);
 // the bits decided per phase are host arithmetic on the range.  Outputs outside [out_lo, out_hi) -- at most 7 in front, the
 // ragged end behind -- are formed and dropped.  A launch covers < 2^31 samples, so every u32 count is exact.
 #include "bbb_common.hpp"
 #include "eye_common.hpp"
+#include "fir_common.hpp"
 #include "tx_common.hpp"
 
 #include <algorithm>
@@ -30,19 +30,7 @@
 namespace bbb {
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kTile = kLinkTile;              // outputs per workgroup step: 8 per thread
-constexpr int kHist = 256;                    // LDS samples in front of a step's first output (8 * ngroups are formed)
-constexpr int kLdsWords = (kHist + kTile) / 2 + 4;
-
-typedef short v2s __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ inline int dot2(uint32_t x, uint32_t h, int acc) {
-    return __builtin_amdgcn_sdot2(__builtin_bit_cast(v2s, x), __builtin_bit_cast(v2s, h), acc, false);
-}
-
-__device__ inline int sat16(int v) { return min(max(v, -32768), 32767); }
 
 struct LinkRaw { unsigned long long nz, bw; };
 
@@ -97,8 +85,8 @@ __device__ inline uint4 shape8(const LinkLaunch &a, const int16_t *T, unsigned c
 }
 
 template <bool HIST>
-__global__ __launch_bounds__(kThreads) void link_kernel(LinkLaunch a, uint32_t *__restrict scratch) {
-    __shared__ __attribute__((aligned(16))) uint32_t lds[2][kLdsWords];
+__global__ __launch_bounds__(kFirThreads) void link_kernel(LinkLaunch a, uint32_t *__restrict scratch) {
+    __shared__ __attribute__((aligned(16))) uint32_t lds[2][kFirLdsWords];
     __shared__ __attribute__((aligned(16))) int16_t T[8 * 256];
     __shared__ uint32_t H[HIST ? kEyeRows * kEyeLanes : 1];
     __shared__ uint32_t E[8];
@@ -112,11 +100,7 @@ __global__ __launch_bounds__(kThreads) void link_kernel(LinkLaunch a, uint32_t *
             w[k] = ((uint32_t)((int)(int16_t)(v[k] & 0xffffu) >> 4) & 0xffffu) | ((uint32_t)((int)v[k] >> 20) << 16);
         reinterpret_cast<u32x4 *>(T)[t] = w;
     }
-    if constexpr (HIST) {
-        u32x4 *h4 = reinterpret_cast<u32x4 *>(H);
-        for (int i = t; i < kEyeRows * kEyeLanes / 4; i += kThreads) h4[i] = u32x4{0u, 0u, 0u, 0u};
-    }
-    if (t < 8) E[t] = 0;
+    eye_zero<HIST>(H, E, t, kFirThreads);
     __syncthreads();
 
     const int ng = (int)a.ngroups;
@@ -126,12 +110,12 @@ __global__ __launch_bounds__(kThreads) void link_kernel(LinkLaunch a, uint32_t *
     const long long s00 = a.tb - (long long)a.delay;
     const unsigned d = (unsigned)((s00 - BBB_TX_BIT_SAMPLE0) & 7);             // slots j >= 8 - d belong to the next bit
     const unsigned cb = (unsigned)(((unsigned long long)s00 - a.col_origin) & 63) + 8u * (lane & 7);
-    const uint64_t nsteps = ((uint64_t)(a.out_hi - a.tb) + kTile - 1) / kTile;
+    const uint64_t nsteps = ((uint64_t)(a.out_hi - a.tb) + kLinkTile - 1) / kLinkTile;
     uint32_t err[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 
     // the inputs of a step are loaded one step ahead, as fir_kernel loads its samples
-    auto own = [&](uint64_t step) { return fetch8(a, a.tb + (long long)(step * kTile) + 8 * t); };
-    auto lead = [&](uint64_t step) { return t < ng ? fetch8(a, a.tb + (long long)(step * kTile) - 8 * (t + 1)) : LinkRaw{0, 0}; };
+    auto own = [&](uint64_t step) { return fetch8(a, a.tb + (long long)(step * kLinkTile) + 8 * t); };
+    auto lead = [&](uint64_t step) { return t < ng ? fetch8(a, a.tb + (long long)(step * kLinkTile) - 8 * (t + 1)) : LinkRaw{0, 0}; };
     uint64_t s = blockIdx.x;
     LinkRaw cur{0, 0}, cur_lead{0, 0};
     if (s < nsteps) {
@@ -139,7 +123,7 @@ __global__ __launch_bounds__(kThreads) void link_kernel(LinkLaunch a, uint32_t *
         cur_lead = lead(s);
     }
     for (int par = 0; s < nsteps; s += gridDim.x, par ^= 1) {
-        const long long base = a.tb + (long long)(s * kTile);
+        const long long base = a.tb + (long long)(s * kLinkTile);
         const uint64_t next = s + gridDim.x;
         LinkRaw nxt{0, 0}, nxt_lead{0, 0};
         if (next < nsteps) {
@@ -147,8 +131,8 @@ __global__ __launch_bounds__(kThreads) void link_kernel(LinkLaunch a, uint32_t *
             nxt_lead = lead(next);
         }
         uint32_t *L = lds[par];
-        *reinterpret_cast<uint4 *>(L + kHist / 2 + 4 * t) = shape8(a, T, c0, base + 8 * t, cur);
-        if (t < ng) *reinterpret_cast<uint4 *>(L + kHist / 2 - 4 * (t + 1)) = shape8(a, T, c0, base - 8 * (t + 1), cur_lead);
+        *reinterpret_cast<uint4 *>(L + kFirHist / 2 + 4 * t) = shape8(a, T, c0, base + 8 * t, cur);
+        if (t < ng) *reinterpret_cast<uint4 *>(L + kFirHist / 2 - 4 * (t + 1)) = shape8(a, T, c0, base - 8 * (t + 1), cur_lead);
         const unsigned long long bw = cur.bw;
         cur = nxt;
         cur_lead = nxt_lead;
@@ -158,33 +142,8 @@ __global__ __launch_bounds__(kThreads) void link_kernel(LinkLaunch a, uint32_t *
         const int lo = (int)min((long long)8, max((long long)0, a.out_lo - n0));
         const int hi = (int)min((long long)8, max((long long)0, a.out_hi - n0));
         if (hi <= lo) continue;
-        const int D0 = kHist / 2 + 4 * t;                           // the dword of x[n0], x[n0 + 1]
-        uint4 h4 = *reinterpret_cast<const uint4 *>(L + D0);
-        uint32_t dw[8], al[7];
-        dw[4] = h4.x, dw[5] = h4.y, dw[6] = h4.z, dw[7] = h4.w;
-#pragma unroll
-        for (int k = 4; k < 7; ++k) al[k] = __builtin_amdgcn_alignbyte(dw[k + 1], dw[k], 2);
-        int acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        for (int g = 0; g < ng; ++g) {
-            // dw[k] is dword D0 - 4 g - 4 + k, al[k] its high sample with the low sample of the next (fir_kernel)
-            const uint4 l4 = *reinterpret_cast<const uint4 *>(L + D0 - 4 * (g + 1));
-            dw[0] = l4.x, dw[1] = l4.y, dw[2] = l4.z, dw[3] = l4.w;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) al[k] = __builtin_amdgcn_alignbyte(dw[k + 1], dw[k], 2);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const uint32_t h = a.taps[4 * g + u];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    acc[2 * r + 1] = dot2(dw[4 - u + r], h, acc[2 * r + 1]);
-                    acc[2 * r] = dot2(al[3 - u + r], h, acc[2 * r]);
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < 4; ++k) dw[4 + k] = dw[k];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) al[4 + k] = al[k];
-        }
+        int acc[8];
+        fir_block8(L, t, ng, a.taps, acc);
         // the decisions against the data bits
         const long long F = (n0 - (long long)a.delay - BBB_TX_BIT_SAMPLE0) >> 3;       // floor: the bit of slot 0
         const unsigned at = (unsigned)(F - ((n0 - 17) >> 3) + kBitsBelow);              // where bit F sits in bw
@@ -192,51 +151,20 @@ __global__ __launch_bounds__(kThreads) void link_kernel(LinkLaunch a, uint32_t *
 #pragma unroll
         for (int j = 0; j < 8; j++) {
             const int b = (unsigned)j < 8u - d ? b0 : b1;
-            const unsigned dec = a.strict ? acc[j] > a.threshold : acc[j] >= a.threshold;
-            err[j] += (unsigned)(j >= lo && j < hi && b >= 0) & (dec != (unsigned)b);
+            err[j] += (unsigned)(j >= lo && j < hi && b >= 0) & (eye_decide(acc[j], a.threshold, a.strict) != (unsigned)b);
         }
         if constexpr (HIST) {
             unsigned A[8];
 #pragma unroll
             for (int r = 0; r < 8; r++)
                 A[r] = r >= lo && r < hi ? eye_row(sat16(acc[r] >> a.shift), a.eye_shift) * kEyeLanes + ((cb + r) & 63) : ~0u;
-#pragma unroll
-            for (unsigned sh = 1; sh < 8; sh <<= 1) {                    // A[j] <- A[(j + rot) mod 8]
-                const bool on = rot & sh;
-                unsigned B[8];
-#pragma unroll
-                for (int j = 0; j < 8; j++) B[j] = on ? A[(j + sh) & 7] : A[j];
-#pragma unroll
-                for (int j = 0; j < 8; j++) A[j] = B[j];
-            }
-#pragma unroll
-            for (int j = 0; j < 8; j++)
-                if (A[j] != ~0u) atomicAdd(&H[A[j]], 1u);
+            eye_add8<true>(H, A, rot);
         }
     }
 
-#pragma unroll
-    for (int j = 0; j < 8; j++) {
-        uint32_t e = err[j];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) e += __shfl_xor(e, o);
-        if (lane == 0 && e) atomicAdd(&E[(d + j) & 7], e);
-    }
+    eye_fold_errors(E, err, d, lane);
     __syncthreads();
-
-    // flush: fold the 64 lane-columns to ncols and store the block's partial
-    const unsigned nbins = HIST ? kEyeRows * a.ncols : 0;
-    uint32_t *out = scratch + (unsigned long long)blockIdx.x * (nbins + 8);
-    if constexpr (HIST) {
-        const unsigned lg = 31 - __builtin_clz(a.ncols), fold = kEyeLanes >> lg;
-        for (unsigned bin = t; bin < nbins; bin += kThreads) {
-            const unsigned row = bin >> lg, col = bin & (a.ncols - 1);
-            uint32_t sum = 0;
-            for (unsigned k = 0; k < fold; k++) sum += H[row * kEyeLanes + col + (k << lg)];
-            out[bin] = sum;
-        }
-    }
-    if (t < 8) out[nbins + t] = E[t];
+    eye_flush<HIST, true>(H, E, scratch, HIST ? kEyeRows * a.ncols : 0, a.ncols, t, kFirThreads);
 }
 
 }  // namespace
@@ -246,8 +174,8 @@ int link_grid_blocks(bool hist) {
     BBB_HIP(hipGetDevice(&dev));
     BBB_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
     // one round of resident blocks (a grid-stride loop over the steps): what a CU holds at once, not a count that leaves a tail
-    if (hist) BBB_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, link_kernel<true>, kThreads, 0));
-    else BBB_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, link_kernel<false>, kThreads, 0));
+    if (hist) BBB_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, link_kernel<true>, kFirThreads, 0));
+    else BBB_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, link_kernel<false>, kFirThreads, 0));
     return std::max(cus, 1) * std::max(per_cu, 1);
 }
 
@@ -255,18 +183,12 @@ int link_launch(const LinkLaunch &a, bool hist, uint64_t first, uint64_t n, uint
                 uint64_t *counters, hipStream_t st) {
     if (n == 0) return BBB_OK;
     if (n > kLinkLaunchMax) return fail(BBB_EINVAL, "a link launch covers at most 2^31 samples");
-    const uint64_t nsteps = ((uint64_t)(a.out_hi - a.tb) + kTile - 1) / kTile;
+    const uint64_t nsteps = ((uint64_t)(a.out_hi - a.tb) + kLinkTile - 1) / kLinkTile;
     const unsigned nb = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(nsteps, (uint64_t)blocks));
-    if (hist) link_kernel<true><<<nb, kThreads, 0, st>>>(a, scratch);
-    else link_kernel<false><<<nb, kThreads, 0, st>>>(a, scratch);
+    if (hist) link_kernel<true><<<nb, kFirThreads, 0, st>>>(a, scratch);
+    else link_kernel<false><<<nb, kFirThreads, 0, st>>>(a, scratch);
     BBB_HIP(hipGetLastError());
-    const unsigned nbins = hist ? kEyeRows * a.ncols : 0;
-    EyeTubBits tb;
-    eye_tub_bits(first, n, &tb);
-    eye_reduce_kernel<<<(nbins + 8 + 255) / 256, 256, 0, st>>>(scratch, nb, nbins, reinterpret_cast<unsigned long long *>(hist ? hist_out : nullptr),
-                                                               reinterpret_cast<unsigned long long *>(counters), tb);
-    BBB_HIP(hipGetLastError());
-    return BBB_OK;
+    return eye_reduce_launch(scratch, nb, hist ? kEyeRows * a.ncols : 0, hist ? hist_out : nullptr, counters, first, n, st);
 }
 
 }  // namespace bbb

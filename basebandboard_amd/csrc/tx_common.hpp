@@ -1,5 +1,6 @@
-// tx_common.hpp -- device helpers shared by the transmitter's kernels (tx_kernels.hip) and the BER sweep over its
-// settings (txsweep_kernels.hip): the coefficient set as a kernel argument, the 12-bit wrap and the data-bit window.
+// tx_common.hpp -- what the transmitter's kernels (tx_kernels.hip), the BER sweep over its settings (txsweep_kernels.hip),
+// the eye (eye_common.hpp) and the filtered link (link_kernels.hip) share: the coefficient set as a kernel argument, the
+// 12-bit wrap, one entry of the shaped-value table, the data-bit window and the bits a range decides per bathtub phase.
 #pragma once
 
 #include "bbb_common.hpp"
@@ -9,6 +10,31 @@ namespace bbb {
 struct Coeffs64 { int16_t c[64]; };
 
 __device__ __forceinline__ int wrap12_dev(int v) { return (int)((unsigned)v << 20) >> 20; }
+
+// One entry of the shaped-value table: ROM idx contributes +c[8 idx + ph] when data bit M - idx is 1 (bit 7 - idx of q), else
+// -c (bitshaper.py:52-58,:74); the 12-bit wrap of the sum is the adder tree's sample (:76-86).  Every table builder calls
+// this and applies its own layout.
+__device__ __forceinline__ int shaped_entry(const int16_t *coeffs, int ph, int q) {
+    int sum = 0;
+#pragma unroll
+    for (int idx = 0; idx < 8; idx++) {
+        const int c = coeffs[8 * idx + ph];
+        sum += ((q >> (7 - idx)) & 1) ? c : -c;
+    }
+    return wrap12_dev(sum);
+}
+
+// the bits a range of samples decides at each bathtub phase: b[p] counts the m >= 0 with 8m + 45 + p in [first, first + n)
+static inline void tx_phase_bits(uint64_t first, uint64_t n, unsigned long long *b) {
+    const uint64_t last = first + n - 1;
+    for (int p = 0; p < 8; p++) {
+        const uint64_t s = BBB_TX_BIT_SAMPLE0 + p;
+        b[p] = 0;
+        if (last < s) continue;
+        const uint64_t lo = first <= s ? 0 : (first - s + 7) / 8, hi = (last - s) / 8;
+        b[p] = hi >= lo ? hi - lo + 1 : 0;
+    }
+}
 
 // Q bit j = data bit M0-7+j, j = 0..9 (bits before the first one are 0: the reset shift register).
 // `bits` holds data bits m0 .. m0+navail-1 and nothing else may be read: a window reaching past them

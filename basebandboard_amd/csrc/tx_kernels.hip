@@ -10,7 +10,8 @@
 //
 // GPU formulation: sample n depends on 8 consecutive data bits and a phase,
 //     shaped[n] = T[ph][q],  ph = (n-17) & 7,  q = bits M-7..M (oldest in bit 0),  M = (n-17) >> 3,
-// with T (8 x 256 int16, 4 KiB) built per block in LDS from the 64 coefficients.  One thread
+// with T (8 x 256 int16, 4 KiB) built per block in LDS from the 64 coefficients (an entry is
+// shaped_entry of tx_common.hpp, for every table of the library).  One thread
 // produces 16 consecutive samples (two 16-byte stores), reading 16 noise bytes and one 10-bit data
 // window.
 // Roofline: HBM (2 B written + 1 B noise read per sample).
@@ -33,13 +34,7 @@ __global__ void __launch_bounds__(256)
 shaper_table_kernel(Coeffs64 cf, unsigned c0, uint16_t *__restrict TT) {
     for (int e = threadIdx.x; e < 256 * 8; e += blockDim.x) {
         const int q = e >> 3, j = e & 7, ph = (int)((c0 + (unsigned)j) & 7u);
-        int sum = 0;
-#pragma unroll
-        for (int idx = 0; idx < 8; idx++) {
-            const int c = cf.c[8 * idx + ph];
-            sum += ((q >> (7 - idx)) & 1) ? c : -c;
-        }
-        TT[e] = (uint16_t)(wrap12_dev(sum) & 0xffff);
+        TT[e] = (uint16_t)(shaped_entry(cf.c, ph, q) & 0xffff);
     }
 }
 
@@ -81,17 +76,8 @@ tx_waveform_kernel(Coeffs64 cf, const unsigned long long *__restrict bits, long 
                    const int8_t *__restrict noise, int noise_var, int bit_en, int noise_en,
                    unsigned long long first_sample, unsigned long long nsamples, int16_t *__restrict out) {
     __shared__ int16_t T[8 * 256];
-    // T[ph][q]: ROM idx contributes +c[8 idx + ph] when data bit M-idx is 1 (q bit 7-idx), else -c
-    for (int e = threadIdx.x; e < 8 * 256; e += blockDim.x) {
-        const int ph = e >> 8, q = e & 255;
-        int s = 0;
-#pragma unroll
-        for (int idx = 0; idx < 8; idx++) {
-            const int c = cf.c[8 * idx + ph];
-            s += ((q >> (7 - idx)) & 1) ? c : -c;
-        }
-        T[e] = (int16_t)wrap12_dev(s);
-    }
+    // T[ph][q] (shaped_entry, tx_common.hpp)
+    for (int e = threadIdx.x; e < 8 * 256; e += blockDim.x) T[e] = (int16_t)shaped_entry(cf.c, e >> 8, e & 255);
     __syncthreads();
     // 16 samples per thread: one 16-byte noise load, two 16-byte stores, one 10-bit data window
     const unsigned long long ngroups = (nsamples + 15) / 16;

@@ -19,11 +19,7 @@ namespace {
 
 constexpr uint64_t kSweepChunkDefault = 1ull << 26;   // 64 MiB of int8 noise: every launch of a chunk finds it in the Infinity Cache
 constexpr uint64_t kSweepChunkMax = 1ull << 30;
-constexpr uint64_t kSweepSampleLimit = 1ull << 62;    // first_sample + nsamples (the transmitter's own range)
 constexpr int kSweepMaxSettings = 512;
-
-// floor(v / 8) for signed v
-int64_t floor8(int64_t v) { return v >= 0 ? v / 8 : -((-v + 7) / 8); }
 
 // the decision x >= t of a setting (strict: x > threshold), t clamped to [-2048, 2048]: x is 12-bit, so nothing changes
 int32_t decision_bound(const bbb_tx_setting &s) {
@@ -161,8 +157,7 @@ int bbb_tx_ber_sweep_run(bbb_tx_ber_sweep *s, uint64_t first_sample, uint64_t ns
     if (!s) return fail(BBB_EINVAL, "null sweep object");
     if (!counters_dev) return fail(BBB_EINVAL, "null counters_dev");
     if ((uintptr_t)counters_dev & 7) return fail(BBB_EINVAL, "misaligned device pointer");
-    if (first_sample > kSweepSampleLimit || nsamples > kSweepSampleLimit - first_sample)
-        return fail(BBB_EINVAL, "first_sample + nsamples must be <= 2^62");
+    if (const int rc = tx_range_check(first_sample, nsamples)) return rc;
     if (nsamples == 0) return BBB_OK;
     if (s->any_noise && s->base.warmup + first_sample + nsamples < nsamples)
         return fail(BBB_EINVAL, "warmup + first_sample + nsamples overflows");

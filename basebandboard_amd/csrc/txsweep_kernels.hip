@@ -21,7 +21,8 @@
 //  - slot j of every 8-aligned group of samples has the same bathtub phase (d + j) mod 8, so per setting the errors sit in
 //    8 packed registers (two 16-bit counters each) -- no histogram.
 // A block reduces per wave, writes its partial with plain stores to a scratch slab, and a small kernel folds the slab in
-// u64 (no global atomics), adding the bits decided per phase, which the host knows exactly from the range.
+// u64 (no global atomics), adding the bits decided per phase, which the host knows exactly from the range (tx_phase_bits of
+// tx_common.hpp, the eye's and the link's too).
 // Every per-thread 16-bit counter stays below 2 * kSweepMaxIters * 64 < 2^16, and a launch covers < 2^31 samples.
 #include "bbb_common.hpp"
 #include "tx_common.hpp"
@@ -46,16 +47,8 @@ __global__ void __launch_bounds__(256)
 txsweep_table_kernel(const int16_t *__restrict coeffs, uint16_t *__restrict tables) {
     const int16_t *cf = coeffs + 64 * blockIdx.x;
     uint16_t *T = tables + 8 * 256 * blockIdx.x;
-    for (int e = threadIdx.x; e < 8 * 256; e += blockDim.x) {
-        const int ph = e >> 8, q = e & 255;
-        int s = 0;
-#pragma unroll
-        for (int idx = 0; idx < 8; idx++) {
-            const int c = cf[8 * idx + ph];
-            s += ((q >> (7 - idx)) & 1) ? c : -c;
-        }
-        T[e] = (uint16_t)(((unsigned)wrap12_dev(s) * 16u + 8u) & 0xffffu);
-    }
+    for (int e = threadIdx.x; e < 8 * 256; e += blockDim.x)
+        T[e] = (uint16_t)(((unsigned)shaped_entry(cf, e >> 8, e & 255) * 16u + 8u) & 0xffffu);
 }
 
 // the 16 samples of one thread's group: noise bytes nz, data window Q of bits M0-7 .. M0+2, sample e has (n - 17) mod 8 =
@@ -179,18 +172,6 @@ txsweep_reduce_kernel(const uint32_t *__restrict scratch, unsigned blocks, unsig
     }
 }
 
-// the bits a range of samples decides at each phase: m >= 0 with 8m + 45 + p in [first, first + n)
-static void sweep_bits(uint64_t first, uint64_t n, unsigned long long *b) {
-    const uint64_t last = first + n - 1;
-    for (int p = 0; p < 8; p++) {
-        const uint64_t s = BBB_TX_BIT_SAMPLE0 + p;
-        b[p] = 0;
-        if (last < s) continue;
-        const uint64_t lo = first <= s ? 0 : (first - s + 7) / 8, hi = (last - s) / 8;
-        b[p] = hi >= lo ? hi - lo + 1 : 0;
-    }
-}
-
 int sweep_tables_launch(const int16_t *coeffs_dev, int ntab, uint16_t *tables, hipStream_t st) {
     if (ntab <= 0) return BBB_OK;
     txsweep_table_kernel<<<ntab, 256, 0, st>>>(coeffs_dev, tables);
@@ -247,7 +228,7 @@ int sweep_launch(const SweepGroup &g, const uint16_t *tables, const SweepChunk &
         o.idx[2 * k] = k < g.pairs ? g.idx[2 * k] : -1;
         o.idx[2 * k + 1] = k < g.pairs ? g.idx[2 * k + 1] : -1;
     }
-    sweep_bits(c.first, c.n, o.bits);
+    tx_phase_bits(c.first, c.n, o.bits);
     const unsigned groups = (unsigned)((c.n + 15) / 16);
     const uint16_t *tab = tables + (uint64_t)g.table * 8 * 256;
     unsigned nb = 0;
