@@ -17,6 +17,7 @@ from .nco import NCO, NCOState                           # noqa: F401
 from .sinc import SincInterpolator                       # noqa: F401
 from .fir import FIR, FIRStream                          # noqa: F401
 from .link import LinkSweep                              # noqa: F401
+from .errstat import ErrorStats                          # noqa: F401
 from .grngstats import (clt_pmf, clt_pmf_delivered, moments, chi_square, tail_table, pdf_cdf, evaluate,  # noqa: F401
                         evaluate_samples)
-from . import gf2, recurrences, grngstats                # noqa: F401
+from . import gf2, recurrences, grngstats, errstat                # noqa: F401

@@ -21,6 +21,8 @@ SYMBOLS = [
     "bbb_prbs_detector_run", "bbb_prbs_detector_stream", "bbb_ber_trials", "bbb_ber_trials_dev", "bbb_ber_run_open", "bbb_ber_run_next", "bbb_ber_run_next_dev", "bbb_ber_run_tell", "bbb_ber_run_close", "bbb_ber_sweep_multi", "bbb_sweep_shard", "bbb_multi_last_info", "bbb_multi_release", "bbb_shaper_fill_i16", "bbb_tx_fill_i16", "bbb_tx_stream_open", "bbb_tx_stream_next", "bbb_tx_stream_read", "bbb_tx_stream_seek", "bbb_tx_stream_tell", "bbb_tx_stream_close", "bbb_rx_slice", "bbb_rx_phase_search", "bbb_eye_accumulate_i16", "bbb_tx_eye_open", "bbb_tx_eye_run", "bbb_tx_eye_close", "bbb_tx_ber_sweep_open", "bbb_tx_ber_sweep_run", "bbb_tx_ber_sweep_close", "bbb_acf_accumulate_i16", "bbb_tx_acf_open", "bbb_tx_acf_run", "bbb_tx_acf_close", "bbb_nco_rom", "bbb_nco_open", "bbb_nco_set_cfg", "bbb_nco_set_stream", "bbb_nco_run", "bbb_nco_get_state", "bbb_nco_set_state", "bbb_nco_close", "bbb_sinc_coefficients", "bbb_sinc_interpolate", "bbb_sinc_eye_open", "bbb_sinc_eye_run", "bbb_sinc_eye_close", "bbb_fir_moving_average", "bbb_fir_filter", "bbb_fir_slice", "bbb_link_sweep_open", "bbb_link_sweep_run", "bbb_link_sweep_close", "bbb_gf2_berlekamp_massey", "bbb_gf2_recur",
     "bbb_gf2_dot", "bbb_gf2_poly_is_primitive", "bbb_gf2_poly_modexp", "bbb_lutopt_charpoly", "bbb_lutopt_is_full_period",
     "bbb_lutopt_save_matrix_file", "bbb_lutopt_search_candidate", "bbb_lutopt_search",
+    "bbb_errstat_open", "bbb_errstat_accumulate", "bbb_errstat_skip", "bbb_errstat_read", "bbb_errstat_reset",
+    "bbb_errstat_set_stream", "bbb_errstat_geometry", "bbb_errstat_close",
 ]
 
 
@@ -92,6 +94,22 @@ class FirCfg(C.Structure):
     """bbb_fir_cfg"""
     _fields_ = [("ntaps", C.c_uint32), ("taps", C.c_int16 * 256), ("shift", C.c_uint32), ("decim", C.c_uint32),
                 ("phase", C.c_uint32), ("out_bytes", C.c_uint32)]
+
+
+ERRSTAT_NBINS = 312
+
+
+class ErrstatCfg(C.Structure):
+    """bbb_errstat_cfg"""
+    _fields_ = [("guard", C.c_uint32), ("nblock", C.c_uint32), ("block_bits", C.c_uint64 * 4)]
+
+
+class ErrstatResult(C.Structure):
+    """bbb_errstat_result"""
+    _fields_ = ([(n, C.c_uint64) for n in ("bits", "errors", "first_error", "last_error", "max_gap", "bursts", "burst_len_sum",
+                                           "max_burst_len", "max_burst_weight", "open_first", "open_last", "open_weight")]
+                + [("errored_blocks", C.c_uint64 * 4)]
+                + [(n, C.c_uint64 * ERRSTAT_NBINS) for n in ("gap_hist", "burst_len_hist", "burst_weight_hist")])
 
 
 class Ber(C.Structure):
@@ -214,6 +232,14 @@ def lib():
                                       C.POINTER(EyeCfg), u64, C.POINTER(vp)]
     l.bbb_link_sweep_run.argtypes = [vp, u64, u64, vp, vp]
     l.bbb_link_sweep_close.argtypes = [vp]
+    l.bbb_errstat_open.argtypes = [C.POINTER(ErrstatCfg), i32, vp, C.POINTER(vp)]
+    l.bbb_errstat_accumulate.argtypes = [vp, vp, vp, u64]
+    l.bbb_errstat_skip.argtypes = [vp, u64]
+    l.bbb_errstat_read.argtypes = [vp, C.POINTER(ErrstatResult)]
+    l.bbb_errstat_reset.argtypes = [vp]
+    l.bbb_errstat_set_stream.argtypes = [vp, vp]
+    l.bbb_errstat_geometry.argtypes = [u64p, u64p]
+    l.bbb_errstat_close.argtypes = [vp]
     u8p = C.POINTER(C.c_uint8)
     l.bbb_gf2_berlekamp_massey.argtypes = [u8p, u64, u8p, C.POINTER(C.c_int64)]
     l.bbb_gf2_recur.argtypes = [i32, i32, u64p, u8p, i32, u8p]

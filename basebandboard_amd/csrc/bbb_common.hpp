@@ -233,4 +233,20 @@ int hist_samples_launch(const void *samples, int elem, uint64_t nsamples, unsign
 // hist[b] += the `used` partials
 int hist_reduce_launch(const uint32_t *scratch, unsigned used, unsigned nbins, uint64_t *hist, hipStream_t st);
 
+// errstat_kernels.hip: gap, burst and errored-block statistics of a packed error stream (include/bbb.h, bbb_errstat_*)
+constexpr uint64_t kErrWaveBits = 65536;          // one wavefront: 8 steps of 64 lanes x 2 words
+constexpr uint64_t kErrTileBits = 4 * kErrWaveBits;   // one workgroup of 4 wavefronts
+constexpr uint64_t kErrLaunchBits = 1ull << 34;   // bits per launch: 65536 tile summaries
+struct ErrLaunch {                                // one launch: nbits <= kErrLaunchBits from the position in res->bits
+    const uint64_t *err, *mask;                   // mask may be nullptr
+    uint64_t nbits;
+    uint32_t guard, nblock;
+    uint64_t block[4];                            // the first nblock in use; 0: unused entry
+    int vec;                                      // err and mask are 16-byte aligned: 16-byte loads
+};
+size_t errstat_scratch_bytes();                   // the tile summaries of one launch
+// the tile kernel and the stitch behind it: counters and carried state in *res (device) move on by nbits
+int errstat_launch(const ErrLaunch &a, bbb_errstat_result *res, void *scratch, hipStream_t st);
+int errstat_skip_launch(bbb_errstat_result *res, uint64_t nbits, hipStream_t st);   // one thread: res->bits += nbits
+
 }  // namespace bbb

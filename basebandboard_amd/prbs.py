@@ -74,11 +74,22 @@ class PRBSErrorDetector:
                                                     self.device, _stream_ptr(self.device)), "bbb_prbs_detector_run")
         return err, reload
 
-    def run_stream(self, packed, nbits, want_err=False, want_reload=False, chunk_bits=0, warm_bits=0):
+    def run_stream(self, packed, nbits, want_err=False, want_reload=False, chunk_bits=0, warm_bits=0, error_stats=None):
         """The same machine over ONE long packed stream (bit t at word t//64, LSB first), executed in
         parallel chunks with state hand-off; exact (bbb_prbs_detector_stream).  Returns a dict of
         totals (errors = err while reload == 0, errors_raw, reload_clocks, resyncs, ...) and, when
-        asked for, the packed `err` / `reload` streams as int64 CUDA tensors."""
+        asked for, the packed `err` / `reload` streams as int64 CUDA tensors.  error_stats: an errstat.ErrorStats that is fed
+        the call's `err` stream with `reload` as its mask (the clocks `errors` counts); both streams are then produced
+        whether asked for or not."""
+        if error_stats is not None:
+            want_e, want_r = want_err, want_reload
+            out = self.run_stream(packed, nbits, True, True, chunk_bits, warm_bits)
+            error_stats.accumulate(out["err"], out["reload"], int(nbits))
+            if not want_e:
+                del out["err"]
+            if not want_r:
+                del out["reload"]
+            return out
         if packed.dtype != torch.int64 or not packed.is_cuda or not packed.is_contiguous():
             raise ValueError("packed must be a contiguous int64 CUDA tensor")
         if packed.numel() * 64 < nbits:

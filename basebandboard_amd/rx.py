@@ -78,11 +78,12 @@ class RX:
         bits, nbits = self.slice(samples, first_sample, stride, rx_filter=rx_filter)
         return self.prbsdet.count_errors(bits, nbits, first_bit=first_bit, init=prbs_init), nbits
 
-    def detect(self, samples, first_sample=0, stride=None, want_err=False, want_reload=False, rx_filter=None):
+    def detect(self, samples, first_sample=0, stride=None, want_err=False, want_reload=False, rx_filter=None, error_stats=None):
         """Slice at this receiver's `sample_delay`, then the exact self-synchronising detector over the
-        whole stream (rx.py:41-46 at scale): totals as PRBSErrorDetector.run_stream returns them."""
+        whole stream (rx.py:41-46 at scale): totals as PRBSErrorDetector.run_stream returns them.  error_stats: an
+        errstat.ErrorStats that is fed the detector's errors (PRBSErrorDetector.run_stream)."""
         bits, nbits = self.slice(samples, first_sample, stride, rx_filter=rx_filter)
-        return self.prbsdet.run_stream(bits, nbits, want_err=want_err, want_reload=want_reload)
+        return self.prbsdet.run_stream(bits, nbits, want_err=want_err, want_reload=want_reload, error_stats=error_stats)
 
     def interpolate(self, samples, shift=4, out_dtype=torch.int16):
         """The capture at 16 times its sample rate (sinc.SincInterpolator.interpolate, gateware/bbb/sinc.py): an int16 CUDA

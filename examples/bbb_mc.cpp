@@ -28,6 +28,10 @@
 //                       setting decided on the raw sample (bbb_tx_ber_sweep_*) and behind the moving average of rx.py:24-26
 //                       (bbb_link_sweep_* with the taps of bbb_fir_moving_average, the filtered stream re-timed by `delay`), the
 //                       waveform never materialised: one JSON line per phase with the bits decided and both error counts
+//          errstat:     --errstat 1 [--bits 1e8] [--prbs 31] [--guard 64]   how errors are distributed (bbb_errstat_*): a PRBS stream
+//                       with a bit flipped every 99991 positions and one burst of 3 k flipped bits, through the exact detector
+//                       (bbb_prbs_detector_stream) into the error statistics with `reload` as the mask: one JSON line with the
+//                       totals, the gaps, the bursts (the open one closed on the host) and the errored blocks of 1e3 .. 1e6 bits
 //          spectrum:    --spectrum FILE [--lags 256] [--eye-samples 1e6] [--prbs 31] [--nv 8] [--shape 16]   autocorrelation
 //                       counters of the transmitter's waveform (bbb_tx_acf_*) and the power spectrum from them (Bartlett lag
 //                       window, mean removed, one-sided, fs = 1): FILE gets a CSV k,freq,psd,psd_db (psd_db is nan in a bin
@@ -190,7 +194,8 @@ int main(int argc, char **argv) {
     int lags = 256;
     int shape = 16, eye_shift = 4;
     double eye_samples = 1e6;
-    int tx_sweep = 0, nv_lo = 0, nv_hi = 15, fir = 0, link = 0, link_delay = 2;
+    int tx_sweep = 0, nv_lo = 0, nv_hi = 15, fir = 0, link = 0, link_delay = 2, errstat = 0;
+    unsigned long errstat_guard = 64;
     unsigned long long init0 = 1;
     double bits = 1e9, from = 0, to = 10, step = 1, loopback = 0, nsamples = 0, grng_eval = 0;
     unsigned long long first_step = 0;
@@ -238,6 +243,8 @@ int main(int argc, char **argv) {
         else if (a == "--fir") fir = std::atoi(v);
         else if (a == "--link") link = std::atoi(v);
         else if (a == "--delay") link_delay = std::atoi(v);
+        else if (a == "--errstat") errstat = std::atoi(v);
+        else if (a == "--guard") errstat_guard = std::strtoul(v, nullptr, 0);
         else if (a == "--nv-range") {
             if (std::sscanf(v, "%d:%d", &nv_lo, &nv_hi) != 2) { std::fprintf(stderr, "--nv-range A:B\n"); return 2; }
         }
@@ -288,6 +295,69 @@ int main(int argc, char **argv) {
         std::fclose(f);
         std::printf("{\"mode\": \"nco\", \"samples\": %llu, \"fcw\": %lu, \"am\": %lu, \"pa\": %u, \"q\": %d, \"w\": %d, \"y\": %d, "
                     "\"seconds\": %.6f}\n", (unsigned long long)n, nco_fcw, nco_am, st.pa, st.q, st.w, st.y, dt);
+        return 0;
+    }
+
+    // ---- how the detector's errors are distributed (the reference's own detector test injects isolated errors and a burst,
+    // gateware/bbb/prbs.py:129-138) ------------------------------------------------------------------------------------------
+    if (errstat) {
+        if (bits < 1024 || bits > 1e11 || errstat_guard >= (1ull << 32)) { std::fprintf(stderr, "--bits 1024..1e11, --guard < 2^32\n"); return 2; }
+        const uint64_t n = (uint64_t)bits, nw = (n + 63) / 64;
+        uint64_t *buf = nullptr, *err = nullptr, *rl = nullptr;
+        if (hipMalloc((void **)&buf, nw * 8) != hipSuccess || hipMalloc((void **)&err, nw * 8) != hipSuccess ||
+            hipMalloc((void **)&rl, nw * 8) != hipSuccess) {
+            std::fprintf(stderr, "hipMalloc failed\n");
+            return 1;
+        }
+        CHECK(bbb_prbs_fill(k, 1, 0, n, buf, 0, nullptr));
+        // flips: one word at a time through the host (a handful of words; the stream itself stays on the device)
+        std::vector<uint64_t> flips;
+        for (uint64_t t = 4096; t < n; t += 99991) flips.push_back(t);
+        for (uint64_t t = n / 2; t < n / 2 + 3 * (uint64_t)k && t < n; ++t) flips.push_back(t);
+        for (uint64_t t : flips) {
+            uint64_t w = 0;
+            if (hipMemcpy(&w, buf + t / 64, 8, hipMemcpyDeviceToHost) != hipSuccess) { std::fprintf(stderr, "copy failed\n"); return 1; }
+            w ^= 1ull << (t % 64);
+            if (hipMemcpy(buf + t / 64, &w, 8, hipMemcpyHostToDevice) != hipSuccess) { std::fprintf(stderr, "copy failed\n"); return 1; }
+        }
+        const bbb_errstat_cfg cfg = {(uint32_t)errstat_guard, 4, {1000, 10000, 100000, 1000000}};
+        bbb_errstat *e = nullptr;
+        CHECK(bbb_errstat_open(&cfg, 0, nullptr, &e));
+        bbb_detector_stats ds{};
+        const double t0 = now_s();
+        CHECK(bbb_prbs_detector_stream(k, buf, n, err, rl, &ds, 0, 0, 0, nullptr));
+        const double t1 = now_s();
+        CHECK(bbb_errstat_accumulate(e, err, rl, n));
+        std::vector<bbb_errstat_result> rv(1);
+        bbb_errstat_result &r = rv[0];
+        CHECK(bbb_errstat_read(e, &r));
+        const double t2 = now_s();
+        CHECK(bbb_errstat_close(e));
+        (void)hipFree(buf);
+        (void)hipFree(err);
+        (void)hipFree(rl);
+        // the burst still open at the end of the data counts as a burst here
+        unsigned long long bursts = r.bursts, len_sum = r.burst_len_sum, max_len = r.max_burst_len, max_w = r.max_burst_weight;
+        if (r.open_weight) {
+            const unsigned long long len = r.open_last - r.open_first + 1;
+            ++bursts;
+            len_sum += len;
+            if (len > max_len) max_len = len;
+            if (r.open_weight > max_w) max_w = r.open_weight;
+        }
+        unsigned long long isolated = r.burst_weight_hist[1] + (r.open_weight == 1 ? 1 : 0);
+        std::printf("{\"mode\": \"errstat\", \"prbs\": %d, \"bits\": %llu, \"flipped\": %llu, \"guard\": %lu, \"errors\": %llu, "
+                    "\"errors_raw\": %llu, \"resyncs\": %llu, \"first_error\": %llu, \"last_error\": %llu, \"max_gap\": %llu, "
+                    "\"bursts\": %llu, \"isolated\": %llu, \"mean_burst_len\": %.3f, \"max_burst_len\": %llu, \"max_burst_weight\": %llu, "
+                    "\"block_bits\": [1000, 10000, 100000, 1000000], \"errored_blocks\": [%llu, %llu, %llu, %llu], "
+                    "\"detector_seconds\": %.6f, \"errstat_seconds\": %.6f}\n",
+                    k, (unsigned long long)r.bits, (unsigned long long)flips.size(), errstat_guard, (unsigned long long)r.errors,
+                    (unsigned long long)ds.errors_raw, (unsigned long long)ds.resyncs, (unsigned long long)r.first_error,
+                    (unsigned long long)r.last_error, (unsigned long long)r.max_gap, bursts, isolated,
+                    bursts ? (double)len_sum / (double)bursts : 0.0, max_len, max_w, (unsigned long long)r.errored_blocks[0],
+                    (unsigned long long)r.errored_blocks[1], (unsigned long long)r.errored_blocks[2],
+                    (unsigned long long)r.errored_blocks[3], t1 - t0, t2 - t1);
+        if (r.errors != ds.errors) { std::fprintf(stderr, "the statistics count %llu errors, the detector %llu\n", (unsigned long long)r.errors, (unsigned long long)ds.errors); return 1; }
         return 0;
     }
 

@@ -737,6 +737,46 @@ typedef struct {
 int bbb_lutopt_search(int k, uint64_t seed, uint64_t first_candidate, uint64_t ncandidates, uint64_t *found_index,
                       uint16_t *taps_out, uint32_t *row_off_out, bbb_search_stats *stats, int device, void *hip_stream);
 
+/* ---- error statistics of a packed error stream: gaps, bursts, errored blocks ------------------ */
+
+/* How the errors of a packed stream (bit t at word t/64, bit t%64: the layout of bbb_prbs_fill and of
+ * bbb_prbs_detector_stream's err_packed_dev) are distributed.  The error positions are the t with err[t] & ~mask[t]; with
+ * mask = the detector's reload stream these are the clocks bbb_detector_stats.errors counts.  Positions are absolute over the life of
+ * an object: the first bit of the first call is position 0 and every call continues where the previous one ended.  With the
+ * positions e_0 < e_1 < ...:
+ *   bin(v) = v for v < 256, 256 + floor(log2 v) - 8 above: every histogram has BBB_ERRSTAT_NBINS entries, entry 0 stays 0.
+ *   gaps:   g_i = e_i - e_(i-1), gap_hist[bin(g_i)]++, max_gap; the stretches before e_0 and behind the last error are no gaps.
+ *   bursts: one starts at e_0 and at every e_i with g_i > guard (guard 0: every error is its own burst) and is closed when the
+ *           next one starts: first f, last l, w errors give burst_len_hist[bin(l - f + 1)]++, burst_weight_hist[bin(w)]++,
+ *           bursts++, burst_len_sum += l - f + 1 and the two maxima.  The burst still open at the end of the data is in none of
+ *           these: it is open_first, open_last, open_weight (0: there is none); closing it is the caller's decision.
+ *   blocks: errored_blocks[j] = number of distinct floor(e_i / block_bits[j]) (blocks aligned to position 0; 0: unused entry).
+ * All counters and the carried state (the previous error, the open burst, the running position) live on the device:
+ * accumulate and skip do not synchronise.  Pointers need 8-byte alignment.  nbits = 0 is a valid no-op; bits beyond nbits in
+ * the last word are ignored.  A call whose nbits is not a multiple of 64 ends the record: every later accumulate or skip returns
+ * BBB_EINVAL until reset.  Bad cfgs (BBB_EINVAL, checked before the device): nblock > 4, a used block_bits outside [1, 2^40). */
+#define BBB_ERRSTAT_NBINS 312
+typedef struct { uint32_t guard; uint32_t nblock; uint64_t block_bits[4]; } bbb_errstat_cfg;
+typedef struct {
+    uint64_t bits, errors, first_error, last_error, max_gap;
+    uint64_t bursts, burst_len_sum, max_burst_len, max_burst_weight;
+    uint64_t open_first, open_last, open_weight;
+    uint64_t errored_blocks[4];
+    uint64_t gap_hist[BBB_ERRSTAT_NBINS], burst_len_hist[BBB_ERRSTAT_NBINS], burst_weight_hist[BBB_ERRSTAT_NBINS];
+} bbb_errstat_result;
+typedef struct bbb_errstat bbb_errstat;
+int bbb_errstat_open(const bbb_errstat_cfg *cfg, int device, void *hip_stream, bbb_errstat **out);
+int bbb_errstat_accumulate(bbb_errstat *e, const uint64_t *err_packed_dev, const uint64_t *mask_packed_dev /* may be NULL */,
+                           uint64_t nbits);
+int bbb_errstat_skip(bbb_errstat *e, uint64_t nbits);            /* nbits error-free positions that are not read */
+int bbb_errstat_read(bbb_errstat *e, bbb_errstat_result *out);   /* host result; synchronises the stream */
+int bbb_errstat_reset(bbb_errstat *e);
+/* Later calls run on hip_stream, ordered behind what is queued on the old one. */
+int bbb_errstat_set_stream(bbb_errstat *e, void *hip_stream);
+/* Host only: the bits one workgroup (tile) and one wavefront of the kernel cover, both multiples of 64. */
+int bbb_errstat_geometry(uint64_t *tile_bits, uint64_t *wave_bits);
+int bbb_errstat_close(bbb_errstat *e);
+
 #ifdef __cplusplus
 }
 #endif
