@@ -24,6 +24,7 @@
 #include "bbb_common.hpp"
 #include "bitslice_util.hpp"
 #include "awgn_launch.hpp"
+#include "stage_common.hpp"
 
 #include <cstdlib>
 #include <mutex>
@@ -756,8 +757,8 @@ awgn256_kernel(const uint32_t *__restrict planes, void *__restrict dst_, unsigne
 // So this kernel stores the 8 count planes of every step as they are -- two 16-byte stores per lane and step, 1 KiB
 // per store instruction, no LDS, no round end -- and the transposition moves into the mover (unplane_kernel), a guest
 // with two waves per CU that runs in the issue slots the sample kernel cannot use.
-// Staging layout: u32x4 stage[wave][step][half][lane], half 0 = planes 0..3, half 1 = planes 4..7 (plane 7 already
-// complemented: the int8 two's complement form).  Every wave runs all L steps (generators beyond G are padding).
+// Staging layout (stage_common.hpp, its definition): u32x4 stage[wave][step][half][lane], half 0 = planes 0..3, half 1 = planes
+// 4..7 (plane 7 already complemented: the int8 two's complement form).  Every wave runs all L steps (generators beyond G are padding).
 // (Tried: [wave][lane >> 3][step][half][lane & 7], which makes a mover unit's 32 KiB ONE contiguous block instead of 256 lines
 // out of 256 different 1 KiB rows.  Slower: noise 1.085 -> 1.19 ms per 1e9 at one read per kernel, the shaping mover's
 // calls 1.44 -> 1.77 ms -- a CU's burst then falls on few memory channels; scattered lines spread over all of them.)
@@ -803,20 +804,20 @@ awgn256_planes_kernel(const uint32_t *__restrict planes, u32x4 *__restrict stage
         LUTOPT256_FOR_PARKED_HI(BBB_PARK)
 #undef BBB_PARK
     }
-    u32x4 *out = stage + (wave * L) * 128 + lane;
+    u32x4 *out = stage_row(stage, wave, L, lane);
 #pragma unroll 1
     for (unsigned t = 0; t < L; t += 2) {
         lutopt256_step_parked_hi(a, pa, b, pb, cnt);
         {
         __builtin_nontemporal_store((u32x4){cnt[0], cnt[1], cnt[2], cnt[3]}, out);
-        __builtin_nontemporal_store((u32x4){cnt[4], cnt[5], cnt[6], cnt[7]}, out + 64);
+        __builtin_nontemporal_store((u32x4){cnt[4], cnt[5], cnt[6], cnt[7]}, out + kStageHalfVecs);
         }
         lutopt256_step_parked_hi(b, pb, a, pa, cnt);
         {
-        __builtin_nontemporal_store((u32x4){cnt[0], cnt[1], cnt[2], cnt[3]}, out + 128);
-        __builtin_nontemporal_store((u32x4){cnt[4], cnt[5], cnt[6], cnt[7]}, out + 192);
+        __builtin_nontemporal_store((u32x4){cnt[0], cnt[1], cnt[2], cnt[3]}, out + kStageStepVecs);
+        __builtin_nontemporal_store((u32x4){cnt[4], cnt[5], cnt[6], cnt[7]}, out + kStageStepVecs + kStageHalfVecs);
         }
-        out += 256;
+        out += 2 * kStageStepVecs;
     }
 }
 
@@ -835,9 +836,7 @@ int awgn256_planes_launch(const uint32_t *d_planes, void *stage, unsigned L, uns
 // four: a guest there is bound by latency, not by work -- so the loads are LDS-DMA (global_load_lds_dwordx4: no
 // destination registers, a whole unit in flight per workgroup while the previous one is processed).
 // Unit of work = (source wave w, 8 of its lanes, 128 steps): 32 KiB of planes in, 256 generators x 128 bytes out.
-//   DMA      32 wave-instructions of 1 KiB (8 per wave): a lane fetches 16 bytes of one (step, half) row (8 lanes = one full
-//            128-byte line); the LDS image is laid out for the readers, raw[c = 2 s + half][quad-step qs][lane8][16 B]
-//            (the DMA's destination is lane-linear, its per-lane SOURCE address is free);
+//   DMA      32 wave-instructions of 1 KiB (8 per wave): stage_common.hpp, stage_dma_unit -- shared with the histogram mover;
 //   phase 1  thread (qs, lane8): 8 x ds_read_b128 (a wave reads 1 KiB contiguous), planes8_to_bytes per step, eight 4x4
 //            byte transposes -> for each of the lane's 32 generators the 4 sample bytes of steps 4qs..4qs+3, one
 //            ds_write_b32 each into the generator's 128-byte row of the tile (row = j * 8 + lane8; 16-byte chunk c of a
@@ -855,12 +854,7 @@ int awgn256_planes_launch(const uint32_t *d_planes, void *stage, unsigned L, uns
 // mover's instructions -- taking the divisions out of the loop, the DMA addresses down to one add each and the shaping
 // mover's per-sample selects out (1290 -> 830 instructions per unit; 810 -> 440 for the plain mover) changed its time by
 // nothing, and so did a third raw buffer (two units in flight).  What did help is the ORDER of the units: see Pos below.
-constexpr unsigned kUnplaneRaw = 32 * 1024, kUnplaneLds = 3 * 32 * 1024, kUnplaneLdsTx = kUnplaneLds + 32 * 1024 + 2 * 2048;
-
-struct UnplaneGeom {                 // host computed (unplane_launch_with)
-    unsigned w_lo, ngroups, nunits;  // first source wave of the window; ceil(L / 128); units = waves x 8 x ngroups
-    unsigned per_block;              // a block takes the units [per_block * blockIdx.x, + per_block) of the order (w, q8, rg)
-};
+constexpr unsigned kUnplaneRaw = kStageUnitBytes, kUnplaneLds = 3 * kStageUnitBytes, kUnplaneLdsTx = kUnplaneLds + 32 * 1024 + 2 * 2048;
 
 // NOWRAP (shaping mover only, round 5): the host has shown that no sample can leave the 12-bit range -- max over the phases of
 // sum |coeffs| + 128 noise_var <= 2047 (unplane_tx_nowrap: true of every coefficient set the reference ships up to noise_var 11) -- so
@@ -870,7 +864,7 @@ struct UnplaneGeom {                 // host computed (unplane_launch_with)
 template <bool TXM, bool NOWRAP = false>
 __global__ void __launch_bounds__(256, 7)      // <= 72 registers: a wave of this kernel must fit beside the sample kernel's (<= 440 of 512)
 unplane_kernel(const u32x4 *__restrict stage, char *__restrict dst, unsigned long long win_lo, unsigned long long nbytes_, unsigned L,
-               unsigned long long G, UnplaneGeom ge, TxFuse tx) {
+               unsigned long long G, StageGeom ge, TxFuse tx) {
     // DYNAMIC shared memory: with a static array of this size hipcc derives "at most one wave per SIMD" from the LDS size
     // and enforces it by declaring 257 registers for this kernel -- which then cannot share a SIMD with the sample
     // kernel's wave (measured: half of the sample waves waited for the mover to leave)
@@ -925,43 +919,16 @@ unplane_kernel(const u32x4 *__restrict stage, char *__restrict dst, unsigned lon
     // of its first and last line belongs to the neighbouring step groups, and those now pass through the same L2 within
     // microseconds instead of through eight different ones (with a block stride over the units the eight lanes-of-eight of
     // one (wave, step group) ran at the same time on eight XCDs, and every line left its L2 partly written).
-    struct Pos { unsigned q8, rg, w; };
-    auto advance = [&](Pos &p) {
-        if (++p.rg == ge.ngroups) {
-            p.rg = 0;
-            if (++p.q8 == 8) { p.q8 = 0; p.w++; }
-        }
-    };
-    const unsigned voff_lane = (lane & 7) * 16 + (lane >> 3) * 8192;      // a lane's 16 bytes of its row; rows 4 steps (8 KiB) apart
-    // the 8 DMA instructions of this wave for a unit into raw buffer `buf`: 1 KiB block b = wv * 8 + k holds
-    // c = b >> 2 = 2 wv + (k >> 2) (step-in-quad s = wv, half = k >> 2) of quad-steps (k & 3) * 8 .. + 8
-    auto dma_unit = [&](const Pos &p, unsigned buf) {
-        const unsigned step0 = p.rg * 128;
-        const unsigned long long wabs = (unsigned long long)ge.w_lo + p.w;
-        const char *const sb = reinterpret_cast<const char *>(stage) + ((wabs * L + step0) * 128 + p.q8 * 8) * 16;
-        uint32_t *const rawb = lds + buf * (kUnplaneRaw / 4) + wv * 8 * 256;
-        if (step0 + 128 <= L) {
-            const char *const pl = sb + wv * 2048 + voff_lane;
-#pragma unroll
-            for (unsigned k = 0; k < 8; k++)
-                __builtin_amdgcn_global_load_lds((const void *)(pl + ((k & 3) * 32 * 2048 + (k >> 2) * 1024)),
-                                                 (lds_void_ptr)(uintptr_t)(rawb + k * 256), 16, 0, 0);
-        } else {
-            // a segment's last unit may be short: phase 2 never writes the missing steps, the DMA re-reads the last one
-            const unsigned last = L - 1 - step0;
-#pragma unroll
-            for (unsigned k = 0; k < 8; k++) {
-                unsigned st = 4 * ((k & 3) * 8 + (lane >> 3)) + wv;
-                st = st < last ? st : last;
-                __builtin_amdgcn_global_load_lds((const void *)(sb + (size_t)st * 2048 + (k >> 2) * 1024 + (lane & 7) * 16),
-                                                 (lds_void_ptr)(uintptr_t)(rawb + k * 256), 16, 0, 0);
-            }
-        }
+    // the DMA instructions of this wave for a unit into raw buffer `buf`: the 8 of the planes, and the shaping mover's two
+    auto dma_unit = [&](const StagePos &p, unsigned buf) {
+        stage_dma_unit(stage, ge, p, L, lds + buf * (kUnplaneRaw / 4), wv, lane);
         if (TXM) {
             // the data bits the unit's pieces will need: per generator the two 32-bit words that hold the windows of its 128
             // samples (16 data bits + 10 of window), fetched like the planes: no registers, landed before phase 2 asks.
             // pu = position in this call of the generator's first sample of the unit (negative when the window starts inside
             // the unit; the buffer leads with 128 zero bits, so the word index stays >= 0)
+            const unsigned step0 = p.rg * kStageUnitSteps;
+            const unsigned long long wabs = (unsigned long long)ge.w_lo + p.w;
             const long long so = (long long)((wabs * 2048 + p.q8 * 8) * (unsigned long long)L + step0) - (long long)win_lo;
 #pragma unroll
             for (unsigned i = 0; i < 2; i++) {
@@ -984,14 +951,10 @@ unplane_kernel(const u32x4 *__restrict stage, char *__restrict dst, unsigned lon
         }
     };
     constexpr unsigned NDMA = TXM ? 10 : 8, NST = TXM ? 16 : 8;      // DMA instructions per unit and wave; stores of a straight-line unit
-    const unsigned u0 = blockIdx.x * ge.per_block;
-    const unsigned n_it = ge.nunits - u0 < ge.per_block ? ge.nunits - u0 : ge.per_block;
-    Pos cur;
-    cur.rg = u0 % ge.ngroups;
-    cur.q8 = (u0 / ge.ngroups) & 7;
-    cur.w = (u0 / ge.ngroups) >> 3;
-    Pos nxt = cur;
-    advance(nxt);
+    StagePos cur;
+    const unsigned n_it = stage_block_units(ge, blockIdx.x, &cur);
+    StagePos nxt = cur;
+    stage_advance(nxt, ge);
     unsigned buf = 0;
     bool fast1 = false;      // wave-uniform: the whole wave took the straight-line store path in the previous unit
     dma_unit(cur, 0);
@@ -1007,15 +970,8 @@ unplane_kernel(const u32x4 *__restrict stage, char *__restrict dst, unsigned lon
         __builtin_amdgcn_s_barrier();
         // ---- phase 1
         {
-            const uint32_t *raw = lds + buf * (kUnplaneRaw / 4) + (qs * 8 + l8) * 4;
             uint32_t Z[4][8];
-#pragma unroll
-            for (unsigned s = 0; s < 4; s++) {
-                const u32x4 lo = *reinterpret_cast<const u32x4 *>(raw + (2 * s) * 1024);
-                const u32x4 hi = *reinterpret_cast<const u32x4 *>(raw + (2 * s + 1) * 1024);
-                Z[s][0] = lo[0]; Z[s][1] = lo[1]; Z[s][2] = lo[2]; Z[s][3] = lo[3];
-                Z[s][4] = hi[0]; Z[s][5] = hi[1]; Z[s][6] = hi[2]; Z[s][7] = TXM ? ~hi[3] : hi[3];      // (TXM: u = g + 128, the unsigned count)
-            }
+            stage_unpack<TXM>(lds + buf * (kUnplaneRaw / 4), tid, Z);      // (TXM: u = g + 128, the unsigned count)
 #pragma unroll
             for (unsigned s = 0; s < 4; s++) planes8_to_bytes(Z[s]);
 #pragma unroll
@@ -1130,7 +1086,7 @@ unplane_kernel(const u32x4 *__restrict stage, char *__restrict dst, unsigned lon
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();           // the tile and raw[buf] are free for the next unit
         cur = nxt;
-        advance(nxt);
+        stage_advance(nxt, ge);
     }
 }
 
@@ -1154,21 +1110,9 @@ static int unplane_launch_with(const void *stage, void *dst, uint64_t win_lo, ui
     int dev = 0, ncu = 256;
     BBB_HIP(hipGetDevice(&dev));
     BBB_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-    // only the source waves whose generators touch the window: generator g owns [g L, (g + 1) L), wave w generators [2048 w, 2048 (w + 1))
-    const uint64_t seg = (uint64_t)L * 2048;
-    const unsigned w_lo = (unsigned)(win_lo / seg);
-    uint64_t w_hi = (win_lo + nbytes + seg - 1) / seg;
-    if (w_hi > nlanes / 64) w_hi = nlanes / 64;
-    const unsigned w_n = (unsigned)(w_hi - w_lo);
-    const unsigned ngroups = (L + 127) / 128;
-    const uint64_t nunits = (uint64_t)w_n * ngroups * 8;
-    if (nunits >> 32) return fail(BBB_EINVAL, "staged window too large for one mover launch (2^32 units of 32 KiB)");
-    uint64_t blocks = (uint64_t)ncu * (uint64_t)env_knob("BBB_UNPLANE_BLOCKS_PER_CU", 1);
-    if (blocks > nunits) blocks = nunits;
-    UnplaneGeom ge;
-    ge.w_lo = w_lo; ge.ngroups = ngroups; ge.nunits = (unsigned)nunits;
-    ge.per_block = (unsigned)((nunits + blocks - 1) / blocks);
-    blocks = (nunits + ge.per_block - 1) / ge.per_block;
+    StageGeom ge;
+    const unsigned blocks = stage_geom(win_lo, nbytes, L, nlanes, (uint64_t)ncu * (uint64_t)env_knob("BBB_UNPLANE_BLOCKS_PER_CU", 1), &ge);
+    if (!blocks) return fail(BBB_EINVAL, "staged window too large for one mover launch (2^32 units of 32 KiB)");
     {
         static std::mutex mu;
         static bool attr_set[64] = {false};
@@ -1181,14 +1125,14 @@ static int unplane_launch_with(const void *stage, void *dst, uint64_t win_lo, ui
         }
     }
     if (tx && unplane_tx_nowrap(*tx)) {
-        hipLaunchKernelGGL((unplane_kernel<true, true>), dim3((unsigned)blocks), dim3(256), kUnplaneLdsTx, st, (const u32x4 *)stage, (char *)dst,
+        hipLaunchKernelGGL((unplane_kernel<true, true>), dim3(blocks), dim3(256), kUnplaneLdsTx, st, (const u32x4 *)stage, (char *)dst,
                            (unsigned long long)win_lo, (unsigned long long)nbytes, L, (unsigned long long)G, ge, *tx);
     } else if (tx) {
-        hipLaunchKernelGGL(unplane_kernel<true>, dim3((unsigned)blocks), dim3(256), kUnplaneLdsTx, st, (const u32x4 *)stage, (char *)dst,
+        hipLaunchKernelGGL(unplane_kernel<true>, dim3(blocks), dim3(256), kUnplaneLdsTx, st, (const u32x4 *)stage, (char *)dst,
                            (unsigned long long)win_lo, (unsigned long long)nbytes, L, (unsigned long long)G, ge, *tx);
     } else {
         TxFuse none{};
-        hipLaunchKernelGGL(unplane_kernel<false>, dim3((unsigned)blocks), dim3(256), kUnplaneLds, st, (const u32x4 *)stage, (char *)dst,
+        hipLaunchKernelGGL(unplane_kernel<false>, dim3(blocks), dim3(256), kUnplaneLds, st, (const u32x4 *)stage, (char *)dst,
                            (unsigned long long)win_lo, (unsigned long long)nbytes, L, (unsigned long long)G, ge, none);
     }
     BBB_HIP(hipGetLastError());

@@ -2,6 +2,7 @@
 // Host logic only: argument checks, GF(2) jump-ahead plans, workspace, kernel launches.
 #include "bbb_common.hpp"
 #include "awgn_launch.hpp"
+#include "stage_common.hpp"
 #include "gf2.hpp"
 #include "rccl_loader.hpp"
 #include "sweep_shard.hpp"
@@ -585,6 +586,12 @@ int queue_mover_with(bbb_lutopt *h, int slot, LaunchMover launch_mover) {
     return BBB_OK;
 }
 
+bool tx_cfg_equal(const bbb_tx_cfg &a, const bbb_tx_cfg &b) {
+    return std::memcmp(a.coeffs, b.coeffs, sizeof a.coeffs) == 0 && a.source == b.source && a.prbs_k == b.prbs_k &&
+           a.prbs_state == b.prbs_state && a.bit_en == b.bit_en && a.noise_en == b.noise_en && a.noise_var == b.noise_var &&
+           a.warmup == b.warmup;
+}
+
 // look-ahead: the first of the fills waiting in a staging slot is taken -- its description is returned, the next one's is left
 bbb_lutopt::Ahead take_ahead(bbb_lutopt *h) {
     const bbb_lutopt::Ahead a = h->ahead;
@@ -594,11 +601,32 @@ bbb_lutopt::Ahead take_ahead(bbb_lutopt *h) {
     return a;
 }
 
-// deliver bytes [win_lo, win_lo + n) of the stream staged in `slot` (partition L, G, nlanes) to dst
-int deliver_i8(bbb_lutopt *h, int slot, void *dst, uint64_t win_lo, uint64_t n, uint64_t L, uint64_t G, unsigned nlanes) {
-    return queue_mover_with(h, slot, [&](const void *stage, hipStream_t ys) {
-        return unplane_launch(stage, dst, win_lo, n, (unsigned)L, G, nlanes, ys);
-    });
+// look-ahead: is the range that waits in a staging slot this very request -- n positions from `first` of a fill of `kind` (1: with
+// the same transmitter configuration: the noise does not depend on it, but a reader who changes it mid-stream gets a fresh
+// kernel)?  Then it is taken (*a) and *waiting is set.
+int take_waiting(bbb_lutopt *h, int kind, uint64_t first, uint64_t n, const bbb_tx_cfg *cfg, bool *waiting, bbb_lutopt::Ahead *a) {
+    *waiting = h->ahead.valid && h->ahead.kind == kind && h->ahead.first == first && h->ahead.n == n &&
+               (kind != 1 || tx_cfg_equal(h->ahead.cfg, *cfg));
+    if (!*waiting) return BBB_OK;
+    // (no begin_op: a delivery queues nothing on an arithmetic stream -- its mover waits for the slot's sample kernel and the
+    // caller's stream by their own events.  Taking the NEXT slot's arithmetic stream here, as rounds 2-3 did, tied that
+    // stream to the running sample kernel with a handover event: the next sample kernel, whose announced start states make
+    // it independent of the running one, then started an event round trip (26-47 us) after it instead of into its tail)
+    if (env_knob("BBB_EXP_DELIVER_HANDOVER", 0)) {
+        const int rc = begin_op(h, true);
+        if (rc) return rc;
+    }
+    *a = take_ahead(h);
+    return BBB_OK;
+}
+
+// look-ahead (bbb_lutopt_set_staged(h, m >= 2)): what the sample kernel of a fill of n produces -- m n, the next m - 1 fills'
+// samples with it, when that stays below `cap` and the stream does not run out: the generator steps from `step` must not wrap,
+// and the positions from `first` must stay below pos_bound (0: no such bound).  Otherwise n
+uint64_t ahead_total(const bbb_lutopt *h, uint64_t n, uint64_t cap, uint64_t step, uint64_t first, uint64_t pos_bound) {
+    const uint64_t m = (uint64_t)h->staged_level;
+    const bool ahead = m >= 2 && (n % 16) == 0 && m * n < cap && step + m * n >= m * n && (!pos_bound || first + m * n < pos_bound);
+    return ahead ? m * n : n;
 }
 
 // produce: the sample kernel for the stream positions the planes in h->cur describe, L steps per generator, into the
@@ -606,7 +634,7 @@ int deliver_i8(bbb_lutopt *h, int slot, void *dst, uint64_t win_lo, uint64_t n, 
 // the mover that last read this slot (bbb_awgn_prefetch on a staged handle), so the arithmetic need not wait for it again.
 int produce_planes(bbb_lutopt *h, uint64_t L, unsigned nlanes, bbb_lutopt::ProfEv *ev, bool planes_seeded_after_mover, int *slot_out,
                    bool small_footprint = false) {
-    const size_t need_words = (size_t)nlanes * (size_t)L * 8;              // nlanes / 64 waves x L steps x 2 KiB
+    const size_t need_words = stage_words(nlanes, L);
     const int slot = h->stage_slot ^= 1;
     *slot_out = slot;
     if (h->ahead.valid && h->ahead.slot == slot) h->ahead.valid = false;            // what waited there is overwritten now
@@ -630,6 +658,48 @@ int produce_planes(bbb_lutopt *h, uint64_t L, unsigned nlanes, bbb_lutopt::ProfE
     if ((rc = mark_planes_read(h))) return rc;
     if (ev) BBB_HIP(hipEventRecord(ev->e2, h->cs));
     return h->stage_arith[slot].record(h->cs);
+}
+
+struct StagedRun { uint64_t L = 0, G = 0; unsigned nlanes = 0; int slot = 0; };      // a staged sample kernel's partition and its slot
+
+// The produce half of EVERY staged call -- the byte fill, the transmitter, the stage visit (bbb_awgn_hist): the sample kernel
+// (its small form or not) for `ntotal` stream positions whose start states are those of `seed_step`, into the next staging slot,
+// and the call's mover behind it.  `hook()` runs between the start states and the sample kernel, on the slot's arithmetic stream
+// (the transmitter's data bits); `launch_mover(run, staging buffer, stream)` queues the mover (queue_mover_with).  `timed`: the
+// call is one that bbb_lutopt_profile times.
+template <typename Hook, typename LaunchMover>
+int staged_produce(bbb_lutopt *h, uint64_t ntotal, uint64_t seed_step, bool small_form, bool timed, Hook hook, LaunchMover launch_mover,
+                   StagedRun *run) {
+    StagedRun &r = *run;
+    uint64_t &L = r.L, &G = r.G;
+    partition(h, ntotal, 16, &L, &G, &r.nlanes);
+    if (L > 0xffffff00ull) return fail(BBB_EINVAL, "nsamples too large for one call (segment length must fit 32 bits): split it");
+    // (a call that will take the announced start states does not depend on the previous sample kernel: see begin_op)
+    int rc = begin_op(h, true, h->pf.matches(seed_step, L, G));
+    if (rc) return rc;
+    h->last_fill_tx = false;            // (what runs on the SIMDs is the plain kernel)
+    bbb_lutopt::ProfEv ev{};
+    const bool prof = timed && h->profiling;
+    if (prof) {
+        BBB_HIP(hipEventCreate(&ev.e0)); BBB_HIP(hipEventCreate(&ev.e1)); BBB_HIP(hipEventCreate(&ev.e2));
+        BBB_HIP(hipEventRecord(ev.e0, h->cs));
+    }
+    bool from_pf = false;
+    if ((rc = acquire_planes(h, seed_step, L, G, r.nlanes, true, &from_pf))) return rc;
+    if ((rc = hook())) return rc;
+    rc = produce_planes(h, L, r.nlanes, prof ? &ev : nullptr, from_pf, &r.slot, small_form);
+    if (!rc) rc = queue_mover_with(h, r.slot, [&](const void *stage, hipStream_t ms) { return launch_mover(r, stage, ms); });
+    if (prof) h->prof_pending.push_back(ev);
+    return rc;
+}
+
+// look-ahead: the sample kernel of `run` produced `left` more fills of n behind the one just delivered, the next one at stream
+// position `first` = generator step `step`
+void record_ahead(bbb_lutopt *h, int kind, uint64_t first, uint64_t step, uint64_t n, uint64_t left, const StagedRun &run) {
+    bbb_lutopt::Ahead &a = h->ahead;
+    a.valid = true; a.kind = kind;
+    a.first = first; a.step = step; a.n = n; a.win_lo = n; a.left = (unsigned)left;
+    a.L = run.L; a.G = run.G; a.nlanes = run.nlanes; a.slot = run.slot;
 }
 
 // the packed n512 kernel's partition: 16 generators per lane, 1024 per wave, segments in multiples of 8 samples (16-byte
@@ -672,57 +742,38 @@ int awgn_fill(bbb_lutopt *h, void *dst, int elem_size, uint64_t nsamples, uint64
     const bool fast256 = h->specialised && elem_size == 1;
     h->last_fill_tx = false;
     const bool staged = fast256 && h->staged_mode && nsamples >= (1ull << 24);
-    // look-ahead: this very range was produced by the previous fill's sample kernel and waits in its staging slot
-    if (staged && h->ahead.valid && h->ahead.kind == 0 && h->ahead.first == first_step && h->ahead.n == nsamples) {
-        // (no begin_op: a delivery queues nothing on an arithmetic stream -- its mover waits for the slot's sample kernel and the
-        // caller's stream by their own events.  Taking the NEXT slot's arithmetic stream here, as rounds 2-3 did, tied that
-        // stream to the running sample kernel with a handover event: the next sample kernel, whose announced start states make
-        // it independent of the running one, then started an event round trip (26-47 us) after it instead of into its tail)
-        if (env_knob("BBB_EXP_DELIVER_HANDOVER", 0)) {
-            int rc0 = begin_op(h, true);
-            if (rc0) return rc0;
-        }
-        const bbb_lutopt::Ahead a = take_ahead(h);
-        return deliver_i8(h, a.slot, dst, a.win_lo, nsamples, a.L, a.G, a.nlanes);
+    if (staged) {
+        // look-ahead: this very range was produced by the previous fill's sample kernel and waits in its staging slot
+        bool waiting;
+        bbb_lutopt::Ahead a;
+        int rc = take_waiting(h, 0, first_step, nsamples, nullptr, &waiting, &a);
+        if (rc) return rc;
+        // the byte mover: bytes [win_lo, win_lo + nsamples) of the stream staged with partition (L, G, nlanes) to dst
+        auto launch_i8 = [&](const void *stage, uint64_t win_lo, uint64_t Lk, uint64_t Gk, unsigned nl, hipStream_t ms) {
+            return unplane_launch(stage, dst, win_lo, nsamples, (unsigned)Lk, Gk, nl, ms);
+        };
+        if (waiting)
+            return queue_mover_with(h, a.slot, [&](const void *stage, hipStream_t ms) { return launch_i8(stage, a.win_lo, a.L, a.G, a.nlanes, ms); });
+        const uint64_t ntotal = ahead_total(h, nsamples, 1ull << 40, first_step, first_step, 0);      // what the sample kernel produces
+        // At one read per sample kernel the noise stream is bound by the kernel's guests (mover, then seeding: together longer than
+        // the kernel): it takes the small form of the kernel, beside which they run at the same time, and that form is given the
+        // state OF its first sample.  With two and more reads per kernel the stream is bound by the kernel: the other form.
+        const bool small_form = h->staged_level == 1 || env_knob("BBB_EXP_NOISE_SMALL", 0);
+        StagedRun run;
+        rc = staged_produce(h, ntotal, first_step + (small_form ? 1 : 0), small_form, true, [] { return BBB_OK; },
+                            [&](const StagedRun &r, const void *stage, hipStream_t ms) { return launch_i8(stage, 0, r.L, r.G, r.nlanes, ms); }, &run);
+        if (!rc && ntotal != nsamples) record_ahead(h, 0, first_step + nsamples, first_step + nsamples, nsamples, ntotal / nsamples - 1, run);
+        return rc;
     }
-    const uint64_t m = (uint64_t)h->staged_level;
-    const bool ahead = staged && m >= 2 && (nsamples % 16) == 0 && m * nsamples < (1ull << 40) &&
-                       first_step + m * nsamples > first_step;
-    const uint64_t ntotal = ahead ? m * nsamples : nsamples;      // what the sample kernel produces
-    if (ahead) {
-        partition(h, ntotal, 16, &L, &G, &nlanes);
-        if (L > 0xffffff00ull) return fail(BBB_EINVAL, "nsamples too large for one call (segment length must fit 32 bits): split it");
-    }
-    // At one read per sample kernel the noise stream is bound by the kernel's guests (mover, then seeding: together longer than
-    // the kernel): it takes the small form of the kernel, beside which they run at the same time, and that form is given the
-    // state OF its first sample.  With two and more reads per kernel the stream is bound by the kernel: the other form.
-    const bool small_form = staged && (h->staged_level == 1 || env_knob("BBB_EXP_NOISE_SMALL", 0));
-    const uint64_t seed_step = first_step + (small_form ? 1 : 0);
-    // (a fill that will take the announced start states does not depend on the previous sample kernel: see begin_op)
-    const bool takes_prefetch = fast256 && h->pf.matches(seed_step, L, G);
-    int rc = begin_op(h, staged, staged && takes_prefetch);
+    int rc = begin_op(h, false);
     if (rc) return rc;
     bbb_lutopt::ProfEv ev{};
     if (h->profiling) {
         BBB_HIP(hipEventCreate(&ev.e0)); BBB_HIP(hipEventCreate(&ev.e1)); BBB_HIP(hipEventCreate(&ev.e2));
         BBB_HIP(hipEventRecord(ev.e0, h->cs));
     }
-    bool from_pf = false;
-    rc = acquire_planes(h, seed_step, L, G, nlanes, fast256, &from_pf);
+    rc = acquire_planes(h, first_step, L, G, nlanes, fast256);
     if (rc) return rc;
-    if (staged) {
-        int slot = 0;
-        rc = produce_planes(h, L, nlanes, h->profiling ? &ev : nullptr, from_pf, &slot, small_form);
-        if (!rc) rc = deliver_i8(h, slot, dst, 0, nsamples, L, G, nlanes);
-        if (h->profiling) h->prof_pending.push_back(ev);
-        if (!rc && ahead) {
-            h->ahead.valid = true; h->ahead.kind = 0;
-            h->ahead.first = h->ahead.step = first_step + nsamples; h->ahead.n = nsamples; h->ahead.win_lo = nsamples;
-            h->ahead.left = (unsigned)m - 1;
-            h->ahead.L = L; h->ahead.G = G; h->ahead.nlanes = nlanes; h->ahead.slot = slot;
-        }
-        return rc;
-    }
     if (fast256) {
         if (h->profiling) BBB_HIP(hipEventRecord(ev.e1, h->cs));
         rc = awgn256_fill_launch(h->cur.buf[kPlanes], (int8_t *)dst, nsamples, (unsigned)L, G, nlanes, h->cs);
@@ -1478,12 +1529,6 @@ static void tx_bit_range(uint64_t first, uint64_t n, int64_t *m0, uint64_t *nbit
     *nbits = hi >= *m0 ? (uint64_t)(hi - *m0 + 1) : 0;
 }
 
-static bool tx_cfg_equal(const bbb_tx_cfg &a, const bbb_tx_cfg &b) {
-    return std::memcmp(a.coeffs, b.coeffs, sizeof a.coeffs) == 0 && a.source == b.source && a.prbs_k == b.prbs_k &&
-           a.prbs_state == b.prbs_state && a.bit_en == b.bit_en && a.noise_en == b.noise_en && a.noise_var == b.noise_var &&
-           a.warmup == b.warmup;
-}
-
 static int tx_check(const bbb_tx_cfg *cfg) {
     if (!cfg) return fail(BBB_EINVAL, "null cfg");
     if (cfg->source != 0 && cfg->source != 1) return fail(BBB_EINVAL, "source must be 0 (PRBS) or 1 (pulse)");
@@ -1571,57 +1616,44 @@ int bbb_tx_fill_i16(bbb_lutopt *h, const bbb_tx_cfg *cfg, int16_t *out_dev, uint
                 return cfg->source == 0 ? prbs_fill_launch(cfg->prbs_k, cfg->prbs_state, (uint64_t)m0, nbits_all, bits64, h->cs)
                                         : pulse_bits_launch(bits64, m0, (nbits_all + 63) / 64, h->cs);
             };
-            auto deliver_tx = [&](int slot, uint64_t win_lo, uint64_t Lk, uint64_t Gk, unsigned nl) {
-                return queue_mover_with(h, slot, [&](const void *stage, hipStream_t ys) {
-                    return unplane_tx_launch(stage, out_dev, win_lo, nsamples, (unsigned)Lk, Gk, nl, cfg->coeffs, d_bits, (uint32_t)(words64 * 2),
-                                             rel, (uint32_t)(F & 7), cfg->noise_var, cfg->bit_en, bits_on ? 1 : 0, ys);
-                });
+            auto launch_tx = [&](const void *stage, uint64_t win_lo, uint64_t Lk, uint64_t Gk, unsigned nl, hipStream_t ys) {
+                return unplane_tx_launch(stage, out_dev, win_lo, nsamples, (unsigned)Lk, Gk, nl, cfg->coeffs, d_bits, (uint32_t)(words64 * 2),
+                                         rel, (uint32_t)(F & 7), cfg->noise_var, cfg->bit_en, bits_on ? 1 : 0, ys);
             };
             // look-ahead (bbb_lutopt_set_staged(h, m >= 2)): the noise of these very samples was produced by an earlier call's
-            // sample kernel and waits in its staging slot (same configuration: the noise does not depend on it, but a reader
-            // who changes it mid-stream gets a fresh kernel, as before)
-            if (h->ahead.valid && h->ahead.kind == 1 && h->ahead.first == first_sample && h->ahead.n == nsamples &&
-                tx_cfg_equal(h->ahead.cfg, *cfg)) {
-                // (no begin_op: see awgn_fill's look-ahead delivery)
-                if (env_knob("BBB_EXP_DELIVER_HANDOVER", 0) && (rc = begin_op(h, true))) return rc;
-                const bbb_lutopt::Ahead a = take_ahead(h);
+            // sample kernel and waits in its staging slot
+            bool waiting;
+            bbb_lutopt::Ahead a;
+            if ((rc = take_waiting(h, 1, first_sample, nsamples, cfg, &waiting, &a))) return rc;
+            if (waiting) {
                 // its data bits sit in the slot's buffer, behind those of the windows before it
                 d_bits = h->d_mbits[a.slot][a.bits_buf]; words64 = a.bits_words64;
                 rel = (uint32_t)(FM - 7 - (a.bits_m0 - 128));
                 bits_on = cfg->bit_en != 0;
-                return deliver_tx(a.slot, a.win_lo, a.L, a.G, a.nlanes);
+                return queue_mover_with(h, a.slot, [&](const void *stage, hipStream_t ys) {
+                    return launch_tx(stage, a.win_lo, a.L, a.G, a.nlanes, ys);
+                });
             }
-            const uint64_t mla = (uint64_t)h->staged_level;
-            // (< 2^34 samples per kernel: the windows' bit offsets into the slot's data-bit buffer are 32-bit)
-            const bool ahead = mla >= 2 && (nsamples % 16) == 0 && mla * nsamples < (1ull << 34) &&
-                               first_sample + mla * nsamples < (1ull << 62) && cfg->warmup + first_sample + mla * nsamples >= mla * nsamples;
-            const uint64_t ntotal = ahead ? mla * nsamples : nsamples;        // what the sample kernel produces
-            partition(h, ntotal, 16, &L, &G, &nlanes);
-            if (L > 0xffffff00ull) return fail(BBB_EINVAL, "nsamples too large for one call (segment length must fit 32 bits): split it");
             const uint64_t step0 = cfg->warmup + first_sample;                // tx.py:70-71
-            const uint64_t seed_step = step0 + 1;      // (the small form of the noise kernel is given the state OF its first sample)
-            const bool takes_prefetch = h->pf.matches(seed_step, L, G);
-            if ((rc = begin_op(h, true, takes_prefetch))) return rc;
-            h->last_fill_tx = false;            // (what runs on the SIMDs is the plain kernel)
-            bool from_pf = false;
-            if ((rc = acquire_planes(h, seed_step, L, G, nlanes, true, &from_pf))) return rc;
+            // (< 2^34 samples per kernel: the windows' bit offsets into the slot's data-bit buffer are 32-bit)
+            const uint64_t ntotal = ahead_total(h, nsamples, 1ull << 34, step0, first_sample, 1ull << 62);      // what the sample kernel produces
             int64_t m0_all;
             uint64_t nbits_all;
             tx_bit_range(first_sample, ntotal, &m0_all, &nbits_all);           // (m0_all == m0: the same first sample)
             bits_on = cfg->bit_en && nbits_all;
-            if ((rc = make_bits(h->stage_slot ^ 1, nbits_all))) return rc;     // (the slot produce_planes takes next)
-            int slot = 0;
-            // (the small-footprint placement of the noise kernel: the transmitter is bound by the kernel's guests -- a shaping
-            // mover per call and the next kernel's seeding -- and beside this placement they run at the same time)
-            if ((rc = produce_planes(h, L, nlanes, nullptr, from_pf, &slot, true))) return rc;
-            if ((rc = deliver_tx(slot, 0, L, G, nlanes))) return rc;
-            if (ahead) {
-                bbb_lutopt::Ahead &a = h->ahead;
-                a.valid = true; a.kind = 1; a.cfg = *cfg;
-                a.first = first_sample + nsamples; a.step = step0 + nsamples;
-                a.n = nsamples; a.win_lo = nsamples; a.left = (unsigned)mla - 1;
-                a.L = L; a.G = G; a.nlanes = nlanes; a.slot = slot;
-                a.bits_m0 = m0; a.bits_words64 = words64; a.bits_buf = bits_buf;
+            // (the small form of the noise kernel, which is given the state OF its first sample: the transmitter is bound by the
+            // kernel's guests -- a shaping mover per call and the next kernel's seeding -- and beside this placement they run at the
+            // same time)
+            StagedRun run;
+            rc = staged_produce(h, ntotal, step0 + 1, true, false,
+                                [&] { return make_bits(h->stage_slot ^ 1, nbits_all); },      // (the slot produce_planes takes next)
+                                [&](const StagedRun &r, const void *stage, hipStream_t ys) { return launch_tx(stage, 0, r.L, r.G, r.nlanes, ys); },
+                                &run);
+            if (rc) return rc;
+            if (ntotal != nsamples) {
+                record_ahead(h, 1, first_sample + nsamples, step0 + nsamples, nsamples, ntotal / nsamples - 1, run);
+                h->ahead.cfg = *cfg;
+                h->ahead.bits_m0 = m0; h->ahead.bits_words64 = words64; h->ahead.bits_buf = bits_buf;
             }
             return BBB_OK;
         }
@@ -2194,20 +2226,10 @@ int lutopt_stage_visit(bbb_lutopt *h, uint64_t nsamples, uint64_t first_step, lu
     if (!h->specialised || h->device < 0) return fail(BBB_EUNSUP, "the staged sample kernel exists for the shipped n256 matrix on a device");
     if (nsamples == 0 || first_step + nsamples < first_step) return fail(BBB_EINVAL, "empty range, or first_step + nsamples overflows");
     BBB_HIP(hipSetDevice(h->device));
-    uint64_t L, G;
-    unsigned nlanes;
-    partition(h, nsamples, 16, &L, &G, &nlanes);
-    if (L > 0xffffff00ull) return fail(BBB_EINVAL, "nsamples too large for one call (segment length must fit 32 bits): split it");
-    h->last_fill_tx = false;
-    const uint64_t seed_step = first_step + 1;            // the small form takes the state OF its first sample
-    int rc = begin_op(h, true, h->pf.matches(seed_step, L, G));
-    if (rc) return rc;
-    bool from_pf = false;
-    if ((rc = acquire_planes(h, seed_step, L, G, nlanes, true, &from_pf))) return rc;
-    int slot = 0;
-    if ((rc = produce_planes(h, L, nlanes, nullptr, from_pf, &slot, true))) return rc;
-    return queue_mover_with(h, slot, [&](const void *stage, hipStream_t ms) {
-        return visit(ctx, stage, nsamples, (unsigned)L, G, nlanes, ms);
-    });
+    StagedRun run;
+    return staged_produce(h, nsamples, first_step + 1, true, false, [] { return BBB_OK; },      // (the small form takes the state OF its first sample)
+                          [&](const StagedRun &r, const void *stage, hipStream_t ms) {
+                              return visit(ctx, stage, nsamples, (unsigned)r.L, r.G, r.nlanes, ms);
+                          }, &run);
 }
 }  // namespace bbb

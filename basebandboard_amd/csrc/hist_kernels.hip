@@ -5,10 +5,10 @@
 //
 // Three kernels:
 //  - hist_planes_kernel, the "histogram mover": a guest beside awgn256_planes_kernel, in unplane_kernel's place.  It fetches the 8
-//    count planes of a unit (source wave, 8 of its lanes, 128 steps: 32 KiB, 32 768 samples) from the staging slot by LDS-DMA,
-//    exactly as the byte mover does (awgn_kernels.hip, unplane_kernel: same unit, same raw image, same order of the units), turns
-//    them into bytes (planes8_to_bytes) and BINS the bytes where the byte mover transposes and stores them: nothing is written
-//    per sample;
+//    count planes of a unit (source wave, 8 of its lanes, 128 steps: 32 KiB, 32 768 samples) from the staging slot by LDS-DMA
+//    and unpacks them with the reader every mover of the staged stream uses (stage_common.hpp: the unit, its raw image, the
+//    order of the units), turns them into bytes (planes8_to_bytes) and BINS the bytes where the byte mover transposes and
+//    stores them: nothing is written per sample;
 //  - hist_samples_kernel: the same binning over int8 / int16 samples in memory, for every generator the planes form does not
 //    exist for (k = 16 .. 128, 512, table-driven matrices) and for short ranges.  Correct, not fast;
 //  - hist_reduce_kernel: hist[b] += the blocks' partials, in u64.  No global atomics.
@@ -19,6 +19,7 @@
 // 2^30 to the mover and 2^26 to the plain kernel), so every partial count is exact.
 #include "bbb_common.hpp"
 #include "bitslice_util.hpp"
+#include "stage_common.hpp"
 
 #include <algorithm>
 #include <mutex>
@@ -28,15 +29,10 @@ namespace bbb {
 typedef uint32_t hist_u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr unsigned kHistLanes = 64;
-constexpr unsigned kHistRaw = 32 * 1024;                                  // one unit's count planes
+constexpr unsigned kHistRaw = kStageUnitBytes;                            // one unit's count planes
 constexpr unsigned kHistTable = 256 * kHistLanes * 4;                     // 64 KiB: the block's histogram, at the start of the LDS
 constexpr unsigned kHistPlanesLds = kHistTable + 2 * kHistRaw;            // 128 KiB of the CU's 160
 constexpr int kHistSampleThreads = 1024;
-
-struct HistGeom {                    // host computed (hist_planes_launch), as UnplaneGeom
-    unsigned ngroups, nunits;        // ceil(L / 128); units = waves x 8 x ngroups
-    unsigned per_block;              // a block takes the units [per_block * blockIdx.x, + per_block) of the order (w, q8, rg)
-};
 
 // bin `bin` of a block's table: the sum over the 64 lane columns, read ROTATED by the bin (thread t starts at column t mod 64):
 // the 64 threads of a wave then read 64 different banks at every step
@@ -47,7 +43,7 @@ __device__ __forceinline__ uint32_t hist_fold(const uint32_t *H, unsigned bin) {
 }
 
 __global__ void __launch_bounds__(256, 7)      // <= 72 registers: a wave of this kernel must fit beside the sample kernel's
-hist_planes_kernel(const hist_u32x4 *__restrict stage, unsigned long long nsamples, unsigned L, HistGeom ge, uint32_t *__restrict scratch) {
+hist_planes_kernel(const hist_u32x4 *__restrict stage, unsigned long long nsamples, unsigned L, StageGeom ge, uint32_t *__restrict scratch) {
     // (dynamic, as unplane_kernel's: a static array of this size makes hipcc declare a register count no guest can have)
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     typedef __attribute__((address_space(3))) void *lds_void_ptr;
@@ -63,72 +59,29 @@ hist_planes_kernel(const hist_u32x4 *__restrict stage, unsigned long long nsampl
     const unsigned l8 = tid & 7, qs = tid >> 3;                           // lane of eight and quad-step this thread bins
     const uint32_t hbase = (uint32_t)(uintptr_t)(lds_void_ptr)H;         // LDS address of the table
     const uint32_t column = lane * 4u;                                    // byte offset of this lane's column in a bin's row
-    struct Pos { unsigned q8, rg, w; };
-    auto advance = [&](Pos &p) {
-        if (++p.rg == ge.ngroups) {
-            p.rg = 0;
-            if (++p.q8 == 8) { p.q8 = 0; p.w++; }
-        }
-    };
-    const unsigned voff_lane = (lane & 7) * 16 + (lane >> 3) * 8192;      // a lane's 16 bytes of its row; rows 4 steps (8 KiB) apart
-    // the 8 DMA instructions of this wave for a unit (unplane_kernel's): 1 KiB block b = wv * 8 + k holds c = 2 wv + (k >> 2)
-    // (step-in-quad wv, half k >> 2) of quad-steps (k & 3) * 8 .. + 8
-    auto dma_unit = [&](const Pos &p, unsigned buf) {
-        const unsigned step0 = p.rg * 128;
-        const char *const sb = reinterpret_cast<const char *>(stage) + (((unsigned long long)p.w * L + step0) * 128 + p.q8 * 8) * 16;
-        uint32_t *const rawb = raw0 + buf * (kHistRaw / 4) + wv * 8 * 256;
-        if (step0 + 128 <= L) {
-            const char *const pl = sb + wv * 2048 + voff_lane;
-#pragma unroll
-            for (unsigned k = 0; k < 8; k++)
-                __builtin_amdgcn_global_load_lds((const void *)(pl + ((k & 3) * 32 * 2048 + (k >> 2) * 1024)),
-                                                 (lds_void_ptr)(uintptr_t)(rawb + k * 256), 16, 0, 0);
-        } else {
-            // a segment's last unit may be short: the steps past L are never counted, the DMA re-reads the last one
-            const unsigned last = L - 1 - step0;
-#pragma unroll
-            for (unsigned k = 0; k < 8; k++) {
-                unsigned st = 4 * ((k & 3) * 8 + (lane >> 3)) + wv;
-                st = st < last ? st : last;
-                __builtin_amdgcn_global_load_lds((const void *)(sb + (size_t)st * 2048 + (k >> 2) * 1024 + (lane & 7) * 16),
-                                                 (lds_void_ptr)(uintptr_t)(rawb + k * 256), 16, 0, 0);
-            }
-        }
-    };
-    const unsigned u0 = blockIdx.x * ge.per_block;
-    const unsigned n_it = u0 >= ge.nunits ? 0u : (ge.nunits - u0 < ge.per_block ? ge.nunits - u0 : ge.per_block);
-    Pos cur;
-    cur.rg = u0 % ge.ngroups;
-    cur.q8 = (u0 / ge.ngroups) & 7;
-    cur.w = (u0 / ge.ngroups) >> 3;
-    Pos nxt = cur;
-    advance(nxt);
+    StagePos cur;
+    const unsigned n_it = stage_block_units(ge, blockIdx.x, &cur);
+    StagePos nxt = cur;
+    stage_advance(nxt, ge);
     unsigned buf = 0;
-    if (n_it) dma_unit(cur, 0);
+    if (n_it) stage_dma_unit(stage, ge, cur, L, raw0, wv, lane);
     for (unsigned it = 0; it < n_it; it++, buf ^= 1) {
         const bool more = it + 1 < n_it;
-        if (more) dma_unit(nxt, buf ^ 1);
+        if (more) stage_dma_unit(stage, ge, nxt, L, raw0 + (buf ^ 1) * (kHistRaw / 4), wv, lane);
         // this unit's DMA has landed: the only vector-memory operations of this kernel are its DMA, 8 per unit and wave, in order
         if (more) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         // ---- bin: the samples of steps 4 qs .. 4 qs + 3 of the 32 generators of lane q8 * 8 + l8
         {
-            const uint32_t *raw = raw0 + buf * (kHistRaw / 4) + (qs * 8 + l8) * 4;
             uint32_t Z[4][8];
-#pragma unroll
-            for (unsigned s = 0; s < 4; s++) {
-                const hist_u32x4 lo = *reinterpret_cast<const hist_u32x4 *>(raw + (2 * s) * 1024);
-                const hist_u32x4 hi = *reinterpret_cast<const hist_u32x4 *>(raw + (2 * s + 1) * 1024);
-                Z[s][0] = lo[0]; Z[s][1] = lo[1]; Z[s][2] = lo[2]; Z[s][3] = lo[3];
-                Z[s][4] = hi[0]; Z[s][5] = hi[1]; Z[s][6] = hi[2]; Z[s][7] = ~hi[3];      // (the staged plane 7 is that of the int8: bin = x + 128)
-            }
+            stage_unpack<true>(raw0 + buf * (kHistRaw / 4), tid, Z);      // (the staged plane 7 is that of the int8: bin = x + 128)
 #pragma unroll
             for (unsigned s = 0; s < 4; s++) planes8_to_bytes(Z[s]);      // Z[s][i] byte q = the bin of generator j = 8 q + i at step 4 qs + s
             // stream position of generator j = 0 of this lane at the thread's first step; generator j is 64 L further each
             const unsigned step = cur.rg * 128 + 4 * qs;
             const unsigned long long span = 64ull * L;
-            const unsigned long long off0 = ((unsigned long long)cur.w * 2048 + cur.q8 * 8 + l8) * L + step;
+            const unsigned long long off0 = (((unsigned long long)ge.w_lo + cur.w) * kStageWaveGens + cur.q8 * 8 + l8) * L + step;
             // byte address of (bin, this lane's column) in ONE V_PERM_B32: byte 0 = the column (4 lane < 256), byte 1 = the bin
 #define BBB_HIST_ADD(WORD, Q) \
     asm volatile("ds_add_u32 %0, %1" ::"v"(hbase + __builtin_amdgcn_perm(column, (WORD), 0x0c0c0004u | ((Q) << 8))), "v"(1u) : "memory")
@@ -165,7 +118,7 @@ hist_planes_kernel(const hist_u32x4 *__restrict stage, unsigned long long nsampl
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();           // raw[buf] is free for the unit after next
         cur = nxt;
-        advance(nxt);
+        stage_advance(nxt, ge);
     }
     __syncthreads();
     scratch[(size_t)blockIdx.x * 256 + tid] = hist_fold(H, tid);
@@ -242,17 +195,9 @@ int hist_planes_launch(const void *stage, uint64_t nsamples, unsigned L, unsigne
     if (nsamples == 0 || nsamples > (1ull << 31)) return fail(BBB_EINVAL, "a histogram launch counts 1 .. 2^31 samples");
     if (L == 0 || blocks < 1) return fail(BBB_EINVAL, "bad histogram launch");
     // (the planes form exists for k = 256 only: a block's partial is 256 counts, and `scratch` holds blocks x 256 of them)
-    // only the source waves whose generators have samples below nsamples: wave w owns generators [2048 w, 2048 (w + 1))
-    const uint64_t seg = (uint64_t)L * 2048;
-    const uint64_t w_n = std::min<uint64_t>((nsamples + seg - 1) / seg, nlanes / 64);
-    HistGeom ge;
-    ge.ngroups = (L + 127) / 128;
-    const uint64_t nunits = w_n * ge.ngroups * 8;
-    if (nunits == 0 || nunits >> 32) return fail(BBB_EINVAL, "staged range out of the histogram mover's reach");
-    ge.nunits = (unsigned)nunits;
-    const uint64_t want = std::min<uint64_t>((uint64_t)blocks, nunits);
-    ge.per_block = (unsigned)((nunits + want - 1) / want);
-    const unsigned nb = (unsigned)((nunits + ge.per_block - 1) / ge.per_block);
+    StageGeom ge;      // the window [0, nsamples)
+    const unsigned nb = stage_geom(0, nsamples, L, nlanes, (uint64_t)blocks, &ge);
+    if (!nb) return fail(BBB_EINVAL, "staged range out of the histogram mover's reach");
     int rc = hist_lds_attributes();
     if (rc) return rc;
     hipLaunchKernelGGL(hist_planes_kernel, dim3(nb), dim3(256), kHistPlanesLds, st, (const hist_u32x4 *)stage, (unsigned long long)nsamples, L, ge,

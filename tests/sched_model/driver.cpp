@@ -260,7 +260,7 @@ int main(int argc, char **argv) {
     if (h) CK(bbb_lutopt_destroy(h));
     hipEventDestroy(uev);
     for (auto &st : sets) for (void *p : st) hipFree(p);
-    std::printf("{\"sequences\": %ld, \"calls\": %llu, \"operations_checked\": %llu, \"sequences_with_unordered_access\": %ld}\n", nseq,
-                (unsigned long long)calls, (unsigned long long)model::ops_checked(), bad_sequences);
+    std::printf("{\"sequences\": %ld, \"calls\": %llu, \"operations_checked\": %llu, \"sequences_with_unordered_access\": %ld, \"transcript\": \"%016llx\"}\n",
+                nseq, (unsigned long long)calls, (unsigned long long)model::ops_checked(), bad_sequences, (unsigned long long)model::transcript());
     return bad_sequences ? 1 : 0;
 }

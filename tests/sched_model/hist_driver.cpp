@@ -19,18 +19,18 @@
 
 namespace bbb {
 int hist_grid_blocks() { return 256; }
-int hist_planes_launch(const void *stage, uint64_t, unsigned, unsigned, uint32_t *scratch, int, unsigned *used, hipStream_t st) {
-    model::op(st, "hist_planes_kernel", {stage}, {scratch});
+int hist_planes_launch(const void *stage, uint64_t nsamples, unsigned L, unsigned nlanes, uint32_t *scratch, int blocks, unsigned *used, hipStream_t st) {
+    model::op(st, "hist_planes_kernel" + model::args(nsamples, L, nlanes, blocks), {stage}, {scratch});
     *used = 1;
     return BBB_OK;
 }
-int hist_samples_launch(const void *samples, int, uint64_t, unsigned, uint32_t *scratch, int, unsigned *used, hipStream_t st) {
-    model::op(st, "hist_samples_kernel", {samples}, {scratch});
+int hist_samples_launch(const void *samples, int elem, uint64_t nsamples, unsigned nbins, uint32_t *scratch, int blocks, unsigned *used, hipStream_t st) {
+    model::op(st, "hist_samples_kernel" + model::args(elem, nsamples, nbins, blocks), {samples}, {scratch});
     *used = 1;
     return BBB_OK;
 }
-int hist_reduce_launch(const uint32_t *scratch, unsigned, unsigned, uint64_t *hist, hipStream_t st) {
-    model::op(st, "hist_reduce_kernel", {scratch, hist}, {hist});
+int hist_reduce_launch(const uint32_t *scratch, unsigned used, unsigned nbins, uint64_t *hist, hipStream_t st) {
+    model::op(st, "hist_reduce_kernel" + model::args(used, nbins), {scratch, hist}, {hist});
     return BBB_OK;
 }
 }  // namespace bbb
@@ -192,7 +192,9 @@ int main(int argc, char **argv) {
     if (h) CK(bbb_lutopt_destroy(h));
     hipEventDestroy(uev);
     for (auto &st : sets) for (void *p : st) hipFree(p);
-    std::printf("{\"sequences\": %ld, \"calls\": %llu, \"histograms\": %llu, \"operations_checked\": %llu, \"sequences_with_unordered_access\": %ld}\n",
-                nseq, (unsigned long long)calls, (unsigned long long)hists, (unsigned long long)model::ops_checked(), bad_sequences);
+    std::printf("{\"sequences\": %ld, \"calls\": %llu, \"histograms\": %llu, \"operations_checked\": %llu, \"sequences_with_unordered_access\": %ld, "
+                "\"transcript\": \"%016llx\"}\n",
+                nseq, (unsigned long long)calls, (unsigned long long)hists, (unsigned long long)model::ops_checked(), bad_sequences,
+                (unsigned long long)model::transcript());
     return bad_sequences ? 1 : 0;
 }

@@ -22,7 +22,7 @@
 #include "../../basebandboard_amd/csrc/awgn_launch.hpp"
 
 struct MockStream { int id; model::VC vc; bool destroyed = false; };
-struct MockEvent { bool recorded = false; model::VC vc; };
+struct MockEvent { int id; bool recorded = false; model::VC vc; };      // id: creation number (what the trace and the transcript name it by)
 
 namespace model {
 
@@ -34,6 +34,15 @@ static std::vector<std::string> g_errors;
 static std::vector<std::string> g_trace;        // the operations since the last reset (printed with an error)
 static uint64_t g_seq = 0, g_nops = 0;
 static int g_device = 0;
+// The TRANSCRIPT: a running 64-bit hash (FNV-1a) over every line of the trace -- each operation with its stream number, text and
+// the buffers it reads and writes by their #id, each record, wait, host synchronisation, free and hipStreamQuery answer, events
+// and streams by creation number (never by pointer bits: the value must not depend on the build or the run).  Two schedulers
+// that queue the same operations in the same order on the same streams under the same events have the same transcript.
+static uint64_t g_transcript = 0xcbf29ce484222325ull;
+static void log(const std::string &line) {      // (under g_mu, or single-threaded)
+    for (unsigned char c : line + "\n") g_transcript = (g_transcript ^ c) * 0x100000001b3ull;
+    g_trace.push_back(line);
+}
 
 static void join(VC &a, const VC &b) {
     if (a.size() < b.size()) a.resize(b.size(), 0);
@@ -77,6 +86,10 @@ static void error(const std::string &what) {
     }
 }
 
+static std::string id_of(const void *p) {
+    const Buffer *b = buffer_of(p);
+    return p ? (b ? " #" + std::to_string(b->id) : " #?") : " #-";
+}
 static std::string describe(const Buffer &b) { return "buffer #" + std::to_string(b.id) + " (" + std::to_string(b.size) + " B, " + b.tag + ")"; }
 
 // one operation on a stream
@@ -88,7 +101,11 @@ void op(hipStream_t hs, const std::string &what, std::initializer_list<const voi
     s->vc[(size_t)s->id]++;
     const VC t = s->vc;
     g_nops++;
-    g_trace.push_back("[" + std::to_string(++g_seq) + "] stream " + std::to_string(s->id) + ": " + what);
+    std::string line = "[" + std::to_string(++g_seq) + "] stream " + std::to_string(s->id) + ": " + what + "  reads";
+    for (const void *p : reads) line += id_of(p);
+    line += "  writes";
+    for (const void *p : writes) line += id_of(p);
+    log(line);
     auto access = [&](const void *p, bool write) {
         if (!p) return;
         Buffer *b = buffer_of(p);
@@ -119,7 +136,7 @@ void op(hipStream_t hs, const std::string &what, std::initializer_list<const voi
 
 void host_note(const std::string &what) {
     std::lock_guard<std::mutex> g(g_mu);
-    g_trace.push_back("-- " + what);
+    log("-- " + what);
 }
 
 void reset_trace() {
@@ -130,6 +147,7 @@ void reset_trace() {
 const std::vector<std::string> &errors() { return g_errors; }
 void clear_errors() { g_errors.clear(); }
 uint64_t ops_checked() { return g_nops; }
+uint64_t transcript() { return g_transcript; }
 
 void tag(const void *p, const std::string &t) {
     std::lock_guard<std::mutex> g(g_mu);
@@ -154,7 +172,7 @@ hipError_t hipDeviceGetAttribute(int *v, hipDeviceAttribute_t, int) { *v = 256; 
 hipError_t hipDeviceSynchronize(void) {
     std::lock_guard<std::mutex> g(g_mu);
     for (MockStream *s : g_streams) join(g_host, s->vc);
-    g_trace.push_back("-- hipDeviceSynchronize");
+    log("-- hipDeviceSynchronize");
     return hipSuccess;
 }
 
@@ -178,7 +196,7 @@ hipError_t hipFree(void *p) {
     if (it == g_buffers.end()) { error("hipFree of a pointer that is not the base of a live allocation"); return hipErrorInvalidValue; }
     // (the real call waits for the device: everything issued so far is done before the memory goes away)
     for (MockStream *s : g_streams) join(g_host, s->vc);
-    g_trace.push_back("-- hipFree of buffer #" + std::to_string(it->second.id) + " (" + it->second.tag + ")");
+    log("-- hipFree of buffer #" + std::to_string(it->second.id) + " (" + it->second.tag + ")");
     munmap(it->second.base, it->second.maplen);
     g_buffers.erase(it);
     return hipSuccess;
@@ -208,6 +226,7 @@ hipError_t hipMemcpy(void *dst, const void *src, size_t n, hipMemcpyKind k) {
     hipMemcpyAsync(dst, src, n, k, nullptr);
     std::lock_guard<std::mutex> g(g_mu);
     join(g_host, stream_of(nullptr)->vc);
+    log("-- the host waits for the null stream");
     return hipSuccess;
 }
 hipError_t hipMemsetAsync(void *p, int, size_t, hipStream_t s) { op(s, "memset", {}, {p}); return hipSuccess; }
@@ -215,6 +234,7 @@ hipError_t hipMemset(void *p, int v, size_t n) {
     hipMemsetAsync(p, v, n, nullptr);
     std::lock_guard<std::mutex> g(g_mu);
     join(g_host, stream_of(nullptr)->vc);
+    log("-- the host waits for the null stream");
     return hipSuccess;
 }
 
@@ -231,7 +251,7 @@ hipError_t hipStreamDestroy(hipStream_t s) {                          // (the ob
     if (!s) { error("hipStreamDestroy of the null stream"); return hipErrorInvalidValue; }
     MockStream *m = live_stream(s, "hipStreamDestroy");
     m->destroyed = true;
-    g_trace.push_back("-- hipStreamDestroy(stream " + std::to_string(m->id) + ")");
+    log("-- hipStreamDestroy(stream " + std::to_string(m->id) + ")");
     return hipSuccess;
 }
 // hipStreamQuery: hipSuccess means the host has SEEN everything on the stream complete (it is then synchronised with it);
@@ -246,28 +266,33 @@ hipError_t hipStreamQuery(hipStream_t s) {
         if (m->vc[i] > (i < g_host.size() ? g_host[i] : 0u)) pending = true;
     if (pending) {
         g_coin ^= g_coin << 13; g_coin ^= g_coin >> 7; g_coin ^= g_coin << 17;
-        if (g_coin & 1) { g_trace.push_back("-- hipStreamQuery(stream " + std::to_string(m->id) + "): not ready"); return hipErrorNotReady; }
+        if (g_coin & 1) { log("-- hipStreamQuery(stream " + std::to_string(m->id) + "): not ready"); return hipErrorNotReady; }
         join(g_host, m->vc);
     }
-    g_trace.push_back("-- hipStreamQuery(stream " + std::to_string(m->id) + "): done");
+    log("-- hipStreamQuery(stream " + std::to_string(m->id) + "): done");
     return hipSuccess;
 }
 hipError_t hipStreamSynchronize(hipStream_t s) {
     std::lock_guard<std::mutex> g(g_mu);
     MockStream *m = live_stream(s, "hipStreamSynchronize");
     join(g_host, m->vc);
-    g_trace.push_back("-- hipStreamSynchronize(stream " + std::to_string(m->id) + ")");
+    log("-- hipStreamSynchronize(stream " + std::to_string(m->id) + ")");
     return hipSuccess;
 }
 hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned) {
     std::lock_guard<std::mutex> g(g_mu);
     MockStream *m = live_stream(s, "hipStreamWaitEvent");
     if (e && e->recorded) join(m->vc, e->vc);
-    g_trace.push_back("-- stream " + std::to_string(m->id) + " waits for event " + std::to_string((uintptr_t)e & 0xffff) + (e && e->recorded ? "" : " (never recorded: no wait)"));
+    log("-- stream " + std::to_string(m->id) + " waits for event " + std::to_string(e ? e->id : 0) + (e && e->recorded ? "" : " (never recorded: no wait)"));
     return hipSuccess;
 }
-hipError_t hipEventCreate(hipEvent_t *e) { *e = new MockEvent; return hipSuccess; }
-hipError_t hipEventCreateWithFlags(hipEvent_t *e, unsigned) { *e = new MockEvent; return hipSuccess; }
+static int g_next_event = 0;
+hipError_t hipEventCreate(hipEvent_t *e) {
+    std::lock_guard<std::mutex> g(g_mu);
+    *e = new MockEvent{++g_next_event};
+    return hipSuccess;
+}
+hipError_t hipEventCreateWithFlags(hipEvent_t *e, unsigned) { return hipEventCreate(e); }
 hipError_t hipEventDestroy(hipEvent_t e) { delete e; return hipSuccess; }
 hipError_t hipEventRecord(hipEvent_t e, hipStream_t s) {
     std::lock_guard<std::mutex> g(g_mu);
@@ -275,12 +300,13 @@ hipError_t hipEventRecord(hipEvent_t e, hipStream_t s) {
     join(m->vc, g_host);
     e->recorded = true;
     e->vc = m->vc;
-    g_trace.push_back("-- event " + std::to_string((uintptr_t)e & 0xffff) + " recorded on stream " + std::to_string(m->id));
+    log("-- event " + std::to_string(e ? e->id : 0) + " recorded on stream " + std::to_string(m->id));
     return hipSuccess;
 }
 hipError_t hipEventSynchronize(hipEvent_t e) {
     std::lock_guard<std::mutex> g(g_mu);
     if (e && e->recorded) join(g_host, e->vc);
+    log("-- hipEventSynchronize(event " + std::to_string(e ? e->id : 0) + ")");
     return hipSuccess;
 }
 hipError_t hipEventElapsedTime(float *ms, hipEvent_t, hipEvent_t) { *ms = 1.0f; return hipSuccess; }
@@ -300,19 +326,19 @@ int prbs_state_at_host(int k, uint64_t init_state, uint64_t nbits, uint64_t *sta
     return BBB_OK;
 }
 
-int awgn_seed_launch(int, const uint32_t *d_tabs, const uint32_t *, uint64_t, uint32_t *d_states, uint64_t, unsigned, uint32_t *d_planes,
-                     hipStream_t st, int, int) {
-    op(st, "seeding (levels + bitslice)", {d_tabs, d_states}, {d_states});
+int awgn_seed_launch(int, const uint32_t *d_tabs, const uint32_t *, uint64_t G, uint32_t *d_states, uint64_t, unsigned nlanes, uint32_t *d_planes,
+                     hipStream_t st, int slice_mode, int variant) {
+    op(st, "seeding (levels + bitslice)" + args(G, nlanes, slice_mode, variant), {d_tabs, d_states}, {d_states});
     op(st, "bitslice", {d_states}, {d_planes});
     return BBB_OK;
 }
-int awgn_seed_head_launch(int, const uint32_t *d_tabs, const uint32_t *, uint64_t, uint32_t *d_states, hipStream_t st, const PrbsSeedRide *ride) {
-    if (ride) op(st, "seed_head_kernel (+ PRBS lanes)", {d_tabs, ride->d_tabs}, {d_states, ride->d_planes});
-    else op(st, "seed_head_kernel", {d_tabs}, {d_states});
+int awgn_seed_head_launch(int, const uint32_t *d_tabs, const uint32_t *, uint64_t G, uint32_t *d_states, hipStream_t st, const PrbsSeedRide *ride) {
+    if (ride) op(st, "seed_head_kernel (+ PRBS lanes)" + args(G), {d_tabs, ride->d_tabs}, {d_states, ride->d_planes});
+    else op(st, "seed_head_kernel" + args(G), {d_tabs}, {d_states});
     return BBB_OK;
 }
-int awgn_seed_tail_planes_launch(int, const uint32_t *d_top, uint64_t, const uint32_t *d_states, unsigned, uint32_t *d_planes, hipStream_t st) {
-    op(st, "seed_tail_planes_kernel", {d_top, d_states}, {d_planes});
+int awgn_seed_tail_planes_launch(int, const uint32_t *d_top, uint64_t G, const uint32_t *d_states, unsigned nlanes, uint32_t *d_planes, hipStream_t st) {
+    op(st, "seed_tail_planes_kernel" + args(G, nlanes), {d_top, d_states}, {d_planes});
     return BBB_OK;
 }
 int prbs_seed_planes_launch(int, const uint32_t *d_tabs, const uint32_t *, uint64_t, uint32_t *d_states, unsigned, uint32_t *d_planes, hipStream_t st) {
@@ -336,18 +362,19 @@ int awgn256_fill_launch(const uint32_t *d_planes, int8_t *dst, uint64_t, unsigne
     op(st, "awgn256_kernel (one-kernel form)", {d_planes}, {dst});
     return BBB_OK;
 }
-int awgn256_planes_launch(const uint32_t *d_planes, void *stage, unsigned, unsigned, hipStream_t st, bool small) {
-    op(st, small ? "awgn256_planes_kernel<small>" : "awgn256_planes_kernel", {d_planes}, {stage});
+int awgn256_planes_launch(const uint32_t *d_planes, void *stage, unsigned L, unsigned nlanes, hipStream_t st, bool small) {
+    op(st, (small ? "awgn256_planes_kernel<small>" : "awgn256_planes_kernel") + args(L, nlanes, small), {d_planes}, {stage});
     return BBB_OK;
 }
-int unplane_launch(const void *stage, void *dst, uint64_t win_lo, uint64_t nbytes, unsigned, uint64_t, unsigned, hipStream_t st) {
-    op(st, "unplane_kernel (mover) window [" + std::to_string(win_lo) + ", +" + std::to_string(nbytes) + ")", {stage}, {dst});
+int unplane_launch(const void *stage, void *dst, uint64_t win_lo, uint64_t nbytes, unsigned L, uint64_t G, unsigned nlanes, hipStream_t st) {
+    op(st, "unplane_kernel (mover) window [" + std::to_string(win_lo) + ", +" + std::to_string(nbytes) + ")" + args(L, G, nlanes), {stage}, {dst});
     return BBB_OK;
 }
-int unplane_tx_launch(const void *stage, int16_t *dst, uint64_t, uint64_t, unsigned, uint64_t, unsigned, const int16_t *, const uint32_t *d_bits,
-                      uint32_t, uint32_t, uint32_t, int, int, int use_bits, hipStream_t st) {
-    if (use_bits) op(st, "unplane_kernel<TX> (shaping mover)", {stage, d_bits}, {dst});
-    else op(st, "unplane_kernel<TX> (shaping mover)", {stage}, {dst});
+int unplane_tx_launch(const void *stage, int16_t *dst, uint64_t win_lo, uint64_t nsamples, unsigned L, uint64_t G, unsigned nlanes, const int16_t *,
+                      const uint32_t *d_bits, uint32_t nwords32, uint32_t rel_base, uint32_t c0, int noise_var, int bit_en, int use_bits, hipStream_t st) {
+    const std::string what = "unplane_kernel<TX> (shaping mover)" + args(win_lo, nsamples, L, G, nlanes, nwords32, rel_base, c0, noise_var, bit_en, use_bits);
+    if (use_bits) op(st, what, {stage, d_bits}, {dst});
+    else op(st, what, {stage}, {dst});
     return BBB_OK;
 }
 int awgn256_tx_launch(const uint32_t *d_planes, int16_t *dst, uint64_t, unsigned, uint64_t, unsigned, const int16_t *, const uint32_t *d_bits,
@@ -356,8 +383,8 @@ int awgn256_tx_launch(const uint32_t *d_planes, int16_t *dst, uint64_t, unsigned
     else op(st, "awgn256_kernel<TX>", {d_planes}, {dst});
     return BBB_OK;
 }
-int pulse_bits_launch(uint64_t *dst, int64_t, uint64_t nwords, hipStream_t st) {
-    if (nwords) op(st, "pulse_bits_kernel", {}, {dst});
+int pulse_bits_launch(uint64_t *dst, int64_t m_first, uint64_t nwords, hipStream_t st) {
+    if (nwords) op(st, "pulse_bits_kernel" + args(m_first, nwords), {}, {dst});
     return BBB_OK;
 }
 int widen_i8_i16_launch(const int8_t *src, int16_t *dst, uint64_t, hipStream_t st) {
@@ -402,8 +429,8 @@ int rx_slice_launch(const int16_t *d_samples, uint64_t, uint64_t, uint64_t, int,
     op(st, "rx_slice_kernel", {d_samples}, {d_out});
     return BBB_OK;
 }
-int prbs_fill_launch(int, uint64_t, uint64_t, uint64_t nbits, uint64_t *dst, hipStream_t st, int) {
-    if (nbits) op(st, "prbs_stream_kernel (fill)", {}, {dst});
+int prbs_fill_launch(int, uint64_t, uint64_t first_bit, uint64_t nbits, uint64_t *dst, hipStream_t st, int) {
+    if (nbits) op(st, "prbs_stream_kernel (fill)" + args(first_bit, nbits), {}, {dst});
     return BBB_OK;
 }
 int prbs_check_launch(int, uint64_t, uint64_t, uint64_t nbits, const uint64_t *src, uint64_t *nerr_dev, hipStream_t st) {

@@ -26,5 +26,14 @@ void tag(const void *p, const std::string &t);    // a name for an allocation, f
 const std::vector<std::string> &errors();
 void clear_errors();
 uint64_t ops_checked();
+uint64_t transcript();                            // the running hash over everything logged so far (model.cpp)
+
+// " (a, b, ...)": a launch stub's scalar arguments, appended to its operation text so that the transcript covers them
+template <typename... T>
+std::string args(T... v) {
+    std::string s;
+    ((s += (s.empty() ? " (" : ", ") + std::to_string(v)), ...);
+    return s + ")";
+}
 
 }  // namespace model

@@ -423,3 +423,52 @@ def test_an_untaken_hint_does_not_race_the_next_one(gpu, oracle):
         assert np.array_equal(x[:200_000].cpu().numpy(), m.awgn(u.state_at(p), 0, 200_000, fast=True)), p
         tail = m.awgn(u.state_at(p + x.numel() - 4096), 0, 4096, fast=True)
         assert np.array_equal(x[-4096:].cpu().numpy(), tail), p
+
+
+# The movers' STRAIGHT-LINE DMA path (stage_common.hpp, stage_dma_unit: a unit whose 128 steps all exist).  The shapes above, near
+# 2^24, give L = 64: every unit is a segment's short last one.  With 256 CUs (1024 source waves at most) 300 000 032 samples give
+# L = 144 -- per lane group one full unit and one short one of 16 steps -- and G = 2 083 334 generators, whose last wave holds 518.
+N144 = 300_000_032
+
+
+@pytest.fixture(scope="module")
+def one_kernel_144(gpu):
+    """the one-kernel form of the N144 samples from step 16, on a handle of its own: computed once, never written"""
+    return gpu.CLTGRNG(gpu.LUTOPT.shipped(256)).generate(N144, first_step=16)
+
+
+def test_full_unit_byte_fill_equals_oracle_and_one_kernel_form(gpu, oracle, one_kernel_144):
+    m = oracle.Lutopt(path=oracle.data_path(256))
+    u = gpu.LUTOPT.shipped(256)
+    u.set_staged(True)
+    got = gpu.CLTGRNG(u).generate(N144, first_step=16)
+    assert torch.equal(got, one_kernel_144)
+    assert np.array_equal(got[:4096].cpu().numpy(), m.awgn(u.state_at(16), 0, 4096, fast=True))
+    assert np.array_equal(got[-4096:].cpu().numpy(), m.awgn(u.state_at(16 + N144 - 4096), 0, 4096, fast=True))
+
+
+def test_full_unit_look_ahead_window_starts_inside_a_segment(gpu, one_kernel_144):
+    """the same stream as two fills of one sample kernel: the second is a delivery whose window starts inside a segment"""
+    u, g = _look_ahead_gen(gpu, fills=2)
+    half = N144 // 2
+    assert half % 16 == 0 and half % 144 != 0
+    a = g.generate(half, first_step=16)
+    b = g.generate(half, first_step=16 + half)
+    assert torch.equal(a, one_kernel_144[:half])
+    assert torch.equal(b, one_kernel_144[half:])
+
+
+def test_full_unit_staged_tx_equals_one_kernel_form(gpu):
+    """the shaping mover: one call of 300 000 021 samples (a ragged end), and two look-ahead calls of 150 000 016"""
+    y = gpu.TX(31, 1, 0, 16, 1, 8)
+    x = gpu.TX(31, 1, 0, 16, 1, 8)
+    x.urng.set_staged(True)
+    n = 300_000_021
+    ref = y.generate(N144, first_sample=0)
+    assert torch.equal(x.generate(n, first_sample=0), ref[:n])
+    x.urng.set_staged(True, look_ahead=2)
+    half = N144 // 2
+    a = x.generate(half, first_sample=0)
+    b = x.generate(half, first_sample=half)
+    assert torch.equal(a, ref[:half])
+    assert torch.equal(b, ref[half:])

@@ -103,6 +103,20 @@ def test_scheduler_under_thread_sanitizer(exes):
     assert out["sequences_with_unordered_access"] == 0 and "ThreadSanitizer" not in r.stderr
 
 
+def test_transcript_is_the_same_for_the_same_seed_and_for_both_builds(exes):
+    """The model's transcript -- a hash over every operation, wait, record, synchronisation, free and query answer it logs, with
+    buffers, events and streams named by creation number -- says WHAT the scheduler queued: a refactor of bbb_api.hip must leave it
+    as it was (compare a build against the file before the change with one against the file after it, same seeds).  No value is
+    pinned here: a deliberate scheduler change alters it.  What is held is that it is a function of the call sequence alone."""
+    r1, a = run(exes["asan"], 300, 5)
+    r2, b = run(exes["asan"], 300, 5)
+    r3, c = run(exes["tsan"], 300, 5)
+    assert r1.returncode == 0 and r2.returncode == 0 and r3.returncode == 0, (r1.stderr[-3000:], r3.stderr[-3000:])
+    assert len(a["transcript"]) == 16 and a["transcript"] == b["transcript"] == c["transcript"]
+    _, other = run(exes["asan"], 300, 6)
+    assert other["transcript"] != a["transcript"]
+
+
 @pytest.mark.parametrize("macro,mode,what", [
     ("untaken_hint", "all", "seeding"),
     ("untaken_hint", "hints", "seeding"),

@@ -3,11 +3,13 @@ tests/test_sched_model.py): the REAL bbb_api.hip and the REAL hist_api.hip compi
 replaced by stubs that record what they read and write, and random sequences that mix histograms with fills, announcements,
 staging levels, the noise stream object and a re-bound caller stream (tests/sched_model/hist_driver.cpp).
 
-lutopt_stage_visit restates the staged branch of a fill with the caller's kernel in the mover's place; this is the instrument
-that holds the two in step.  It must come through clean, and two mutants must be FOUND: the slot's "free" event no longer
-standing for a reader on the caller's other stream (the mover_chain rule of test_sched_model.py, here with the histogram mover
-as that reader), and a stage visit that claims to be independent of the previous sample kernel when its start states were not
-announced (its in-line seeding then overwrites start states that kernel still reads)."""
+lutopt_stage_visit runs the produce half every staged call runs (staged_produce in bbb_api.hip) with the caller's kernel in the
+mover's place.  It must come through clean, and two mutants must be FOUND: the slot's "free" event no longer standing for a
+reader on the caller's other stream (the mover_chain rule of test_sched_model.py, here with the histogram mover as that
+reader), and a staged call that claims to be independent of the previous sample kernel when its start states were not
+announced (its in-line seeding then overwrites start states that kernel still reads).  The second removes the independence
+decision of the SHARED path -- staged_produce's `int rc = begin_op(h, true, h->pf.matches(seed_step, L, G));`, the line every staged fill,
+transmitter call and stage visit goes through -- so here it is found on a stage visit or on a fill, whichever comes first."""
 import json
 import subprocess
 
