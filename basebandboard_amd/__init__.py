@@ -18,6 +18,8 @@ from .sinc import SincInterpolator                       # noqa: F401
 from .fir import FIR, FIRStream                          # noqa: F401
 from .link import LinkSweep                              # noqa: F401
 from .errstat import ErrorStats                          # noqa: F401
+from .equalizer import (TxXcorr, capture_xcorr, tx_xcorr, xcorr_counts, pulse_response, mmse_taps,  # noqa: F401
+                        noise_power, TX_BIT_ORIGIN)
 from .grngstats import (clt_pmf, clt_pmf_delivered, moments, chi_square, tail_table, pdf_cdf, evaluate,  # noqa: F401
                         evaluate_samples)
-from . import gf2, recurrences, grngstats, errstat                # noqa: F401
+from . import gf2, recurrences, grngstats, errstat, equalizer                # noqa: F401

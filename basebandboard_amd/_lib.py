@@ -23,6 +23,7 @@ SYMBOLS = [
     "bbb_lutopt_save_matrix_file", "bbb_lutopt_search_candidate", "bbb_lutopt_search",
     "bbb_errstat_open", "bbb_errstat_accumulate", "bbb_errstat_skip", "bbb_errstat_read", "bbb_errstat_reset",
     "bbb_errstat_set_stream", "bbb_errstat_geometry", "bbb_errstat_close",
+    "bbb_xcorr_accumulate_i16", "bbb_tx_xcorr_open", "bbb_tx_xcorr_run", "bbb_tx_xcorr_close",
 ]
 
 
@@ -110,6 +111,11 @@ class ErrstatResult(C.Structure):
                                            "max_burst_len", "max_burst_weight", "open_first", "open_last", "open_weight")]
                 + [("errored_blocks", C.c_uint64 * 4)]
                 + [(n, C.c_uint64 * ERRSTAT_NBINS) for n in ("gap_hist", "burst_len_hist", "burst_weight_hist")])
+
+
+class XcorrCfg(C.Structure):
+    """bbb_xcorr_cfg"""
+    _fields_ = [("spb", C.c_uint32), ("nlags", C.c_uint32), ("origin", C.c_uint64)]
 
 
 class Ber(C.Structure):
@@ -240,6 +246,10 @@ def lib():
     l.bbb_errstat_set_stream.argtypes = [vp, vp]
     l.bbb_errstat_geometry.argtypes = [u64p, u64p]
     l.bbb_errstat_close.argtypes = [vp]
+    l.bbb_xcorr_accumulate_i16.argtypes = [vp, u64, u64, vp, u64, u64, C.POINTER(XcorrCfg), vp, i32, vp]
+    l.bbb_tx_xcorr_open.argtypes = [vp, C.POINTER(TxCfg), C.c_uint32, u64, C.POINTER(vp)]
+    l.bbb_tx_xcorr_run.argtypes = [vp, u64, u64, vp]
+    l.bbb_tx_xcorr_close.argtypes = [vp]
     u8p = C.POINTER(C.c_uint8)
     l.bbb_gf2_berlekamp_massey.argtypes = [u8p, u64, u8p, C.POINTER(C.c_int64)]
     l.bbb_gf2_recur.argtypes = [i32, i32, u64p, u8p, i32, u8p]

@@ -249,4 +249,25 @@ size_t errstat_scratch_bytes();                   // the tile summaries of one l
 int errstat_launch(const ErrLaunch &a, bbb_errstat_result *res, void *scratch, hipStream_t st);
 int errstat_skip_launch(bbb_errstat_result *res, uint64_t nbits, hipStream_t st);   // one thread: res->bits += nbits
 
+// xcorr_kernels.hip: the correlation of samples with their data bits (include/bbb.h, bbb_xcorr_accumulate_i16 / bbb_tx_xcorr_*)
+struct XcorrPlan {
+    int gx, gy;                                   // workgroups over the tiles (gx < 0: the device could not be queried), over the lag groups
+    int xt;                                       // lag groups per lane: 8, 16 or 32
+    uint32_t lw;                                  // lags per row of the grid: xt * spb
+    uint64_t scratch_words;                       // u64 words of the partials slab
+};
+struct XcorrLaunch {                              // one launch: the arguments of bbb_xcorr_accumulate_i16, checked
+    const int16_t *samples;
+    uint64_t nsamples, first_sample;
+    const uint64_t *bits;
+    uint64_t bit0, nbits;
+    uint32_t spb, nlags;
+    uint64_t origin;
+};
+// the grid of launches of up to max_nsamples samples at spb and nlags on the current device
+XcorrPlan xcorr_plan(uint32_t spb, uint32_t nlags, uint64_t max_nsamples);
+int xcorr_launch(const XcorrPlan &p, const XcorrLaunch &l, uint64_t *scratch, int64_t *xc, hipStream_t st);
+// the Pulser's data bits first_bit .. first_bit + 64 nwords - 1, packed as bbb_prbs_fill packs
+int xcorr_pulser_bits_launch(uint64_t *dst, uint64_t first_bit, uint64_t nwords, hipStream_t st);
+
 }  // namespace bbb

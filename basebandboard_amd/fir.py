@@ -6,7 +6,8 @@ a decimator, and the filtered slicer (include/bbb.h, bbb_fir_*).
 `FIR(taps, shift)` holds up to 256 int16 taps with sum |h| <= 65535, which keeps acc within int32: the arithmetic is exact.
 `filter` returns the filtered (and decimated) samples, `slice` the decisions acc >= threshold packed as RX.slice packs them
 without the filtered samples ever reaching memory, `stream` an object that filters a record handed over in pieces.
-`FIR.moving_average()` is the reference's MovingAverage, `FIR.matched(coefficients)` the matched filter of a shaper tap set.
+`FIR.moving_average()` is the reference's MovingAverage, `FIR.matched(coefficients)` the matched filter of a shaper tap set,
+`FIR.mmse(h, ...)` the MMSE filter designed from a measured pulse response (equalizer.py).
 """
 import ctypes as C
 
@@ -42,6 +43,7 @@ class FIR:
         if not 0 <= int(shift) <= 31:
             raise ValueError("shift must be 0..31")
         self.taps, self.shift, self.device = taps, int(shift), int(device)
+        self.design_delay = None          # set by a design that knows where its decision lands (FIR.mmse); link.LinkSweep prefers it
 
     @classmethod
     def moving_average(cls, pipeline=False, shift=0, device=0):
@@ -57,6 +59,18 @@ class FIR:
         """The matched filter of a shaper tap set (bitshaper.rcf_coefficients, PRBSShaper.coefficients[i]): the set
         time-reversed."""
         return cls(list(coefficients)[::-1], shift=shift, device=device)
+
+    @classmethod
+    def mmse(cls, h, spb, cursor, ntaps, noise_power, shift=0, device=0, scale_bits=8):
+        """The MMSE receive filter of a measured pulse response (equalizer.mmse_taps: h from TX.pulse_response or
+        RX.pulse_response, noise_power from equalizer.noise_power).  The design's re-timing is kept as `design_delay`
+        (cursor - argmax |h|), which link.LinkSweep uses in place of delay() when no `delay` is given, so that the decision
+        lands on the cursor."""
+        from .equalizer import mmse_taps
+        taps, delay = mmse_taps(h, spb, cursor, ntaps, noise_power, scale_bits)
+        f = cls(taps.tolist(), shift=shift, device=device)
+        f.design_delay = delay
+        return f
 
     def __len__(self):
         return len(self.taps)

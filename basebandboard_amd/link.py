@@ -5,7 +5,7 @@ bbb_link_sweep_*) -- the question gateware/bbb/rx.py:24-26 leaves open (`MovingA
 
     acc(n) = sum_i h[i] * x(n - i)        z(n) = sat16(acc(n) >> shift)        stream sample n: acc / z at n + delay
 
-(`delay` re-times the stream by the filter's group delay, `FIR.delay()` by default), with the threshold in units of acc as
+(`delay` re-times the stream by the filter's group delay: by default `FIR.design_delay` of a designed filter, else `FIR.delay()`), with the threshold in units of acc as
 `FIR.slice` takes it, and the eye histogram bins z.  `LinkSweep(tx, settings, rx_filter).run(n)` gives the bathtub (and,
 with `eye=`, the histogram) of every setting in one pass over the noise stream; neither the waveform nor the filtered
 stream reaches memory.  `TX.eye(..., rx_filter=)` and `TX.ber_sweep(..., rx_filter=)` go through it.
@@ -24,7 +24,7 @@ MAX_DELAY = 255
 class LinkSweep:
     """bbb_link_sweep_*: bathtub and eye of a TX's waveform behind `rx_filter` (a fir.FIR) for many settings at once, chunk by
     chunk on the generator's stream.  The TX supplies the source, the PRBS and the generator, each txsweep.TxSetting the
-    rest (its threshold is in units of acc).  delay None: rx_filter.delay().  eye: an eye.EyeConfig for histograms of z
+    rest (its threshold is in units of acc).  delay None: rx_filter.design_delay where a design set it (FIR.mmse), else rx_filter.delay().  eye: an eye.EyeConfig for histograms of z
     (ncols, shift, col_origin; its threshold / strict are not used).  Context manager; close it before the TX's generator
     handle goes."""
 
@@ -34,7 +34,10 @@ class LinkSweep:
         self.settings = list(settings)
         if not self.settings:
             raise ValueError("at least one setting")
-        self.delay = rx_filter.delay() if delay is None else int(delay)
+        if delay is None:                  # a designed filter knows its own re-timing; any other filter gives its centroid
+            design = getattr(rx_filter, "design_delay", None)
+            delay = rx_filter.delay() if design is None else design
+        self.delay = int(delay)
         if not 0 <= self.delay < 1 << 32:
             raise ValueError("delay must be 0..255")
         sh = _shaper(tx)

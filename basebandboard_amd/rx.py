@@ -122,6 +122,14 @@ class RX:
         n = samples.numel() if nfirst is None else int(nfirst)
         return psd(capture_acf(samples, nlags, nfirst), n, **psd_kw)
 
+    def pulse_response(self, samples, bits, origin, nlags=None, first_sample=0, bit0=0):
+        """The pulse response of a capture measured against its reference bits (bbb_xcorr_accumulate_i16, equalizer.py) at
+        this receiver's samples_per_bit (1..32): samples[i] is sample first_sample + i, `bits` a packed int64 CUDA tensor
+        from data bit bit0 on (e.g. PRBS.generate), `origin` the sample at which bit 0 has lag 0.  float64 [nlags] (None:
+        8 * samples_per_bit).  The caller aligns bits and capture."""
+        from .equalizer import rx_pulse_response
+        return rx_pulse_response(samples, bits, self.samples_per_bit, origin, nlags, first_sample, bit0)
+
     def phase_search(self, samples, stride=None, strict=False, interpolate=False, shift=4, rx_filter=None):
         """Every setting of the reference's `sample_delay` knob (0 .. samples_per_bit - 1; rx.py:19): the
         detector's totals per phase and the phase with the fewest errors.

@@ -56,7 +56,7 @@ class TX:
         materialised (bbb_tx_eye_*): (hist [256, ncols] uint64, bathtub [8, 2] uint64 = bits, errors per phase).  `eye`: an
         eye.EyeConfig, default 64 columns, shift 4 and col_origin = eye.BIT_SAMPLE0 (column c is bathtub phase c mod 8).
         hist / bathtub given: added to.  rx_filter: a fir.FIR -- eye and bathtub of the stream behind that filter instead,
-        re-timed by `delay` (None: rx_filter.delay()); the histogram bins sat16(acc >> shift), the bathtub decides acc
+        re-timed by `delay` (None: the filter's design_delay where FIR.mmse set one, else rx_filter.delay()); the histogram bins sat16(acc >> shift), the bathtub decides acc
         against the eye's threshold in units of acc (bbb_link_sweep_*, link.py)."""
         if rx_filter is not None:
             from .link import link_eye
@@ -81,14 +81,21 @@ class TX:
         from .spectrum import psd, tx_acf
         return psd(tx_acf(self, nsamples, first_sample, nlags, warmup, chunk_samples), int(nsamples), **psd_kw)
 
+    def pulse_response(self, nsamples, nlags=64, first_sample=0, warmup=16, chunk_samples=0):
+        """The pulse response of `x` measured against the transmitter's own data bits over samples [first_sample,
+        first_sample + nsamples), the waveform never materialised (bbb_tx_xcorr_*, equalizer.py): float64 [nlags], lag l
+        lining up with the shaper's coefficients[l].  What equalizer.mmse_taps / FIR.mmse design a receive filter from."""
+        from .equalizer import tx_pulse_response
+        return tx_pulse_response(self, nsamples, nlags, first_sample, warmup, chunk_samples)
+
     def ber_sweep(self, nsamples, noise_vars=range(16), shape_sels=None, threshold=0, strict=False, first_sample=0, warmup=16,
                   chunk_samples=0, counters=None, rx_filter=None, delay=None):
         """Bathtub of `x` for every (shape_sel, noise_var) of the grid in one pass over the noise stream
         (bbb_tx_ber_sweep_*): [len(shape_sels), len(noise_vars), 8, 2] uint64 = bits, errors per phase, each entry what
         TX.eye's bathtub gives for a TX with that shape_sel and noise_var.  shape_sels None: the TX's own set; bit_en and
         noise_en are the TX's; the decision x >= threshold (x > threshold when strict).  counters given: added to.
-        rx_filter: a fir.FIR -- the bathtub of the stream behind that filter instead, re-timed by `delay` (None:
-        rx_filter.delay()), the threshold then in units of acc (bbb_link_sweep_*, link.py)."""
+        rx_filter: a fir.FIR -- the bathtub of the stream behind that filter instead, re-timed by `delay` (None: the
+        filter's design_delay where FIR.mmse set one, else rx_filter.delay()), the threshold then in units of acc (bbb_link_sweep_*, link.py)."""
         from .txsweep import tx_ber_sweep
         return tx_ber_sweep(self, nsamples, noise_vars, shape_sels, threshold, strict, first_sample, warmup, chunk_samples,
                             counters, rx_filter, delay)

@@ -32,6 +32,9 @@
 //                       with a bit flipped every 99991 positions and one burst of 3 k flipped bits, through the exact detector
 //                       (bbb_prbs_detector_stream) into the error statistics with `reload` as the mask: one JSON line with the
 //                       totals, the gaps, the bursts (the open one closed on the host) and the errored blocks of 1e3 .. 1e6 bits
+//          xcorr:       --xcorr 1 [--lags 64] [--eye-samples 1e6] [--prbs 31] [--shape 16]   the transmitter's pulse response with
+//                       the noise off (bbb_tx_xcorr_*): the waveform correlated with its own data bits, divided by the number of
+//                       terms of each lag, printed beside the coefficient set it was shaped with: one JSON line
 //          spectrum:    --spectrum FILE [--lags 256] [--eye-samples 1e6] [--prbs 31] [--nv 8] [--shape 16]   autocorrelation
 //                       counters of the transmitter's waveform (bbb_tx_acf_*) and the power spectrum from them (Bartlett lag
 //                       window, mean removed, one-sided, fs = 1): FILE gets a CSV k,freq,psd,psd_db (psd_db is nan in a bin
@@ -192,9 +195,10 @@ int main(int argc, char **argv) {
     unsigned long nco_fcw = 1ul << 20, nco_am = 1ul << 14;      // NCOTest's resets (gateware/top.py:54-55)
     double nco_samples = 1e6;
     int lags = 256;
+    bool lags_set = false;
     int shape = 16, eye_shift = 4;
     double eye_samples = 1e6;
-    int tx_sweep = 0, nv_lo = 0, nv_hi = 15, fir = 0, link = 0, link_delay = 2, errstat = 0;
+    int tx_sweep = 0, nv_lo = 0, nv_hi = 15, fir = 0, link = 0, link_delay = 2, errstat = 0, xcorr = 0;
     unsigned long errstat_guard = 64;
     unsigned long long init0 = 1;
     double bits = 1e9, from = 0, to = 10, step = 1, loopback = 0, nsamples = 0, grng_eval = 0;
@@ -235,7 +239,7 @@ int main(int argc, char **argv) {
         else if (a == "--fcw") nco_fcw = std::strtoul(v, nullptr, 0);
         else if (a == "--am") nco_am = std::strtoul(v, nullptr, 0);
         else if (a == "--nco-samples") nco_samples = std::atof(v);
-        else if (a == "--lags") lags = std::atoi(v);
+        else if (a == "--lags") lags = std::atoi(v), lags_set = true;
         else if (a == "--eye-samples") eye_samples = std::atof(v);
         else if (a == "--shape") shape = std::atoi(v);
         else if (a == "--shift") eye_shift = std::atoi(v);
@@ -244,6 +248,7 @@ int main(int argc, char **argv) {
         else if (a == "--link") link = std::atoi(v);
         else if (a == "--delay") link_delay = std::atoi(v);
         else if (a == "--errstat") errstat = std::atoi(v);
+        else if (a == "--xcorr") xcorr = std::atoi(v);
         else if (a == "--guard") errstat_guard = std::strtoul(v, nullptr, 0);
         else if (a == "--nv-range") {
             if (std::sscanf(v, "%d:%d", &nv_lo, &nv_hi) != 2) { std::fprintf(stderr, "--nv-range A:B\n"); return 2; }
@@ -635,6 +640,55 @@ int main(int argc, char **argv) {
                     "\"seconds\": %.4f}\n", (unsigned long long)ntx, k, nv, (unsigned long long)plain.bits, (unsigned long long)plain.errors,
                     (unsigned long long)plain.reload_clocks, (unsigned long long)filt.bits, (unsigned long long)filt.errors,
                     (unsigned long long)filt.reload_clocks, secs);
+        return 0;
+    }
+
+    // ---- the transmitter's pulse response, measured against its own data bits with the noise off ----------------------------
+    if (xcorr) {
+        if (!lags_set) lags = 64;                                   // the coefficient set has 64 entries
+        if (shape < 0 || shape > 31 || eye_samples < 1 || lags < 1 || lags > 512) {
+            std::fprintf(stderr, "--shape 0..31, --eye-samples >= 1, --lags 1..512\n");
+            return 2;
+        }
+        bbb_tx_cfg cfg{};
+        rcf_taps(shape == 31 ? 1.0 : shape * (1.0 / 31), cfg.coeffs);          // tx.py:54: np.linspace(0, 1, 32)
+        cfg.source = 0;
+        cfg.prbs_k = k;
+        cfg.prbs_state = 1;
+        cfg.bit_en = 1;
+        cfg.noise_en = 0;
+        cfg.noise_var = 0;
+        cfg.warmup = 16;
+        const uint64_t init[8] = {init0, 0, 0, 0, 0, 0, 0, 0};
+        bbb_lutopt *h = nullptr;
+        CHECK(bbb_lutopt_create(&h, m.n, m.taps.data(), m.off.data(), init, 0));
+        bbb_tx_xcorr *x = nullptr;
+        CHECK(bbb_tx_xcorr_open(h, &cfg, (uint32_t)lags, 0, &x));
+        int64_t *d = nullptr;
+        if (hipMalloc((void **)&d, (size_t)lags * sizeof(int64_t)) != hipSuccess || hipMemset(d, 0, (size_t)lags * sizeof(int64_t)) != hipSuccess) {
+            std::fprintf(stderr, "hipMalloc failed\n");
+            return 1;
+        }
+        const uint64_t count = (uint64_t)eye_samples;
+        const double t0 = now_s();
+        CHECK(bbb_tx_xcorr_run(x, 0, count, d));
+        std::vector<int64_t> xc((size_t)lags);
+        if (hipMemcpy(xc.data(), d, xc.size() * sizeof(int64_t), hipMemcpyDeviceToHost) != hipSuccess) { std::fprintf(stderr, "hipMemcpy failed\n"); return 1; }
+        const double secs = now_s() - t0;
+        CHECK(bbb_tx_xcorr_close(x));
+        CHECK(bbb_lutopt_destroy(h));
+        (void)hipFree(d);
+        std::printf("{\"mode\": \"xcorr\", \"samples\": %llu, \"prbs\": %d, \"shape\": %d, \"lags\": %d, \"seconds\": %.4f, \"pulse_response\": [",
+                    (unsigned long long)count, k, shape, lags, secs);
+        for (int l = 0; l < lags; l++) {
+            // the terms of lag l: samples n < count with n >= 17 + l and n = 17 + l modulo 8
+            const uint64_t first = (uint64_t)BBB_TX_BIT_ORIGIN + (uint64_t)l;
+            const uint64_t terms = count > first ? (count - first + 7) / 8 : 0;
+            std::printf("%s%.4f", l ? ", " : "", terms ? (double)xc[(size_t)l] / (double)terms : 0.0);
+        }
+        std::printf("], \"coeffs\": [");
+        for (int l = 0; l < lags && l < 64; l++) std::printf("%s%d", l ? ", " : "", (int)cfg.coeffs[l]);
+        std::printf("]}\n");
         return 0;
     }
 

@@ -528,6 +528,42 @@ int bbb_tx_acf_open(bbb_lutopt *h, const bbb_tx_cfg *cfg, uint32_t nlags, uint64
 int bbb_tx_acf_run(bbb_tx_acf *a, uint64_t first_sample, uint64_t nsamples, int64_t *acf_dev);
 int bbb_tx_acf_close(bbb_tx_acf *a);
 
+/* ---- pulse response: the correlation of a waveform with its own data bits ------------------------------------------ */
+
+/* What a link tester measures first: the received samples correlated with the known data bits.  With spb samples per data
+ * bit, bit m >= 0 of sign s[m] = bit ? +1 : -1, absolute sample numbers n and `origin` the sample at which bit 0 has lag 0:
+ * for every sample n in [first_sample, first_sample + nsamples) and every lag l in [0, nlags) with (n - origin - l)
+ * divisible by spb and m = (n - origin - l) / spb >= 0
+ *   xc_dev[l] += s[m] * x[n]           int64, added to modulo 2^64 (never overwritten)
+ * The rule is keyed on samples, so the totals do not depend on how a range is cut into calls (the convention of the bathtub
+ * and of the ACF); terms with m < 0 do not count.  Exact for full-range int16, -32768 included, while the true sums fit
+ * int64.  xc[l] divided by the number of terms of lag l estimates the link's pulse response h[l]: for the transmitter
+ * origin = BBB_TX_BIT_ORIGIN and spb = 8, where bit m contributes coeffs[n - 17 - 8m] to sample n (see the eye section), so
+ * lag l lines up with coeffs[l].
+ * spb is 1, 2, 4, 8, 16 or 32; nlags 1 .. min(64 * spb, BBB_XCORR_MAX_LAGS): a sample never looks back over more than 64
+ * bits; origin <= 2^62.  samples_dev[i] is sample first_sample + i (any 2-byte alignment).  bits_packed_dev holds data bits
+ * bit0 .. bit0 + nbits - 1 LSB first in u64 words, 8-byte aligned, as bbb_prbs_fill writes them (bit0 + nbits <= 2^62).  The
+ * call needs bits max(0, floor((first_sample - origin - (nlags - 1)) / spb)) .. floor((first_sample + nsamples - 1 - origin)
+ * / spb); a bit range that does not cover them is BBB_EINVAL, decided from the numbers alone.  A call whose samples all lie
+ * below bit 0 needs no bits and adds nothing.  nsamples = 0 is a no-op.  Every argument check comes before the device is
+ * touched.  Asynchronous on hip_stream; the call's scratch is a stream-ordered allocation, as bbb_eye_accumulate_i16's. */
+#define BBB_XCORR_MAX_LAGS 1024
+#define BBB_TX_BIT_ORIGIN 17
+typedef struct { uint32_t spb; uint32_t nlags; uint64_t origin; } bbb_xcorr_cfg;
+int bbb_xcorr_accumulate_i16(const int16_t *samples_dev, uint64_t nsamples, uint64_t first_sample,
+                             const uint64_t *bits_packed_dev, uint64_t bit0, uint64_t nbits,
+                             const bbb_xcorr_cfg *cfg, int64_t *xc_dev, int device, void *hip_stream);
+/* Transmitter side: the counters of bbb_xcorr_accumulate_i16 over TX.x (bbb_tx_fill_i16 of *cfg on the handle) with spb 8 and
+ * origin BBB_TX_BIT_ORIGIN, against the bits of the transmitter's source (PRBS-k from prbs_state, or the Pulser), samples
+ * [first_sample, first_sample + nsamples).  nlags 1..512.  The object keeps a copy of *cfg and owns an int16 chunk of
+ * chunk_samples (0: 2^26), the chunk's data bits and the partials; run fills, generates the bits and correlates chunk by
+ * chunk on the handle's stream, adding into xc_dev ([nlags] int64).  nsamples = 0 is a no-op.  Asynchronous.
+ * LIFETIME: as bbb_tx_acf -- close the object BEFORE bbb_lutopt_destroy of its handle. */
+typedef struct bbb_tx_xcorr bbb_tx_xcorr;
+int bbb_tx_xcorr_open(bbb_lutopt *h, const bbb_tx_cfg *cfg, uint32_t nlags, uint64_t chunk_samples, bbb_tx_xcorr **out);
+int bbb_tx_xcorr_run(bbb_tx_xcorr *x, uint64_t first_sample, uint64_t nsamples, int64_t *xc_dev);
+int bbb_tx_xcorr_close(bbb_tx_xcorr *x);
+
 /* ---- numerically controlled oscillator: the board's tone source (gateware/bbb/nco.py) ------------------------------ */
 
 /* NCO(fcw, am, fm, pm) with n = 24, m = 10, p = 16 (nco.py:25-44), clocked once per output sample t:
