@@ -1,7 +1,7 @@
 """basebandboard_amd -- MI355X (gfx950) implementation of basebandboard's AWGN / PRBS Monte-Carlo
 path: LUTOPT uniform generator, CLT Gaussian generator, PRBS generator / error detector, the
 fused BPSK bit-error trial, and the pulse shaper / transmitter output stream, its eye diagram and bathtub, the BER sweep over its settings (raw or behind a receive filter), and its autocorrelation and power spectrum; and the
-numerically controlled oscillator (gateware/bbb/nco.py) the scope's 16x sinc interpolator (gateware/bbb/sinc.py) and the exact integer FIR filter in front of the receiver's decision (gateware/bbb/average.py).  Compute lives in libbbb_hip.so (C ABI: include/bbb.h); these modules
+numerically controlled oscillator (gateware/bbb/nco.py) the scope's 16x sinc interpolator (gateware/bbb/sinc.py) and the exact integer FIR filter in front of the receiver's decision (gateware/bbb/average.py), and the digital down-converter that takes a capture at the NCO's carrier to baseband I/Q or magnitude and phase.  Compute lives in libbbb_hip.so (C ABI: include/bbb.h); these modules
 mirror the reference's Python interface (gateware/bbb/rng.py, prbs.py, bitshaper.py, tx.py, rx.py).
 """
 from .prbs import PRBS, PRBSErrorDetector, TAPS          # noqa: F401
@@ -16,6 +16,7 @@ from .spectrum import TxAcf, capture_acf, tx_acf, psd, MAX_LAGS  # noqa: F401
 from .nco import NCO, NCOState                           # noqa: F401
 from .sinc import SincInterpolator                       # noqa: F401
 from .fir import FIR, FIRStream                          # noqa: F401
+from .ddc import DDC, DDCStream                          # noqa: F401
 from .link import LinkSweep                              # noqa: F401
 from .errstat import ErrorStats                          # noqa: F401
 from .equalizer import (TxXcorr, capture_xcorr, tx_xcorr, xcorr_counts, pulse_response, mmse_taps,  # noqa: F401

@@ -24,6 +24,7 @@ SYMBOLS = [
     "bbb_errstat_open", "bbb_errstat_accumulate", "bbb_errstat_skip", "bbb_errstat_read", "bbb_errstat_reset",
     "bbb_errstat_set_stream", "bbb_errstat_geometry", "bbb_errstat_close",
     "bbb_xcorr_accumulate_i16", "bbb_tx_xcorr_open", "bbb_tx_xcorr_run", "bbb_tx_xcorr_close",
+    "bbb_ddc_run", "bbb_ddc_polar_host",
 ]
 
 
@@ -95,6 +96,14 @@ class FirCfg(C.Structure):
     """bbb_fir_cfg"""
     _fields_ = [("ntaps", C.c_uint32), ("taps", C.c_int16 * 256), ("shift", C.c_uint32), ("decim", C.c_uint32),
                 ("phase", C.c_uint32), ("out_bytes", C.c_uint32)]
+
+
+DDC_IQ16, DDC_IQ32, DDC_POLAR = 0, 1, 2
+
+
+class DdcCfg(C.Structure):
+    """bbb_ddc_cfg"""
+    _fields_ = [("fcw", C.c_uint32), ("pa0", C.c_uint32), ("mode", C.c_uint32)]
 
 
 ERRSTAT_NBINS = 312
@@ -250,6 +259,8 @@ def lib():
     l.bbb_tx_xcorr_open.argtypes = [vp, C.POINTER(TxCfg), C.c_uint32, u64, C.POINTER(vp)]
     l.bbb_tx_xcorr_run.argtypes = [vp, u64, u64, vp]
     l.bbb_tx_xcorr_close.argtypes = [vp]
+    l.bbb_ddc_run.argtypes = [vp, u64, C.c_uint32, u64, C.POINTER(DdcCfg), C.POINTER(FirCfg), vp, u64p, i32, vp]
+    l.bbb_ddc_polar_host.argtypes = [C.c_int16, C.c_int16, C.POINTER(C.c_uint16), C.POINTER(C.c_int16)]
     u8p = C.POINTER(C.c_uint8)
     l.bbb_gf2_berlekamp_massey.argtypes = [u8p, u64, u8p, C.POINTER(C.c_int64)]
     l.bbb_gf2_recur.argtypes = [i32, i32, u64p, u8p, i32, u8p]

@@ -178,6 +178,23 @@ struct FirLaunch {                                // one launch: any number of i
 int fir_launch(const FirLaunch &a, int mode, int grid, hipStream_t st);
 // fir_api.hip: the rules of bbb_fir_cfg (BBB_EINVAL with a detail); slice: shift and out_bytes are not looked at
 int fir_cfg_check(const bbb_fir_cfg *c, bool slice);
+// ... and its taps as the kernels' packed words (zeroed first; returns the groups of four words in use)
+uint32_t fir_pack_taps(const bbb_fir_cfg *c, uint32_t words[BBB_FIR_MAX_TAPS / 2]);
+
+// ddc_kernels.hip: the digital down-converter (include/bbb.h, bbb_ddc_run)
+struct DdcLaunch {                                // one launch: any number of input samples; in .. in_vec, taps as FirLaunch
+    const int16_t *in;
+    void *out;                                    // nout pairs of 4 bytes (IQ16, POLAR) or 8 bytes (IQ32)
+    uint64_t nin, nout;
+    uint32_t nbefore, ngroups, shift, decim, phase;
+    uint32_t first;                               // the absolute number of in[0]; its low 24 bits count
+    uint32_t fcw, pa0;
+    int in_vec, out_vec;
+    uint32_t taps[BBB_FIR_MAX_TAPS / 2];
+    int16_t rom[1024];                            // bbb_nco_rom: travels with the launch, so the oscillator has no device state
+};
+// mode: BBB_DDC_IQ16 / IQ32 / POLAR; cus: the device's compute units (the grid is what their LDS holds at once)
+int ddc_launch(const DdcLaunch &a, int mode, int cus, hipStream_t st);
 
 // link_kernels.hip: eye and bathtub of the shaped link behind a receive filter (include/bbb.h, bbb_link_sweep_*)
 constexpr int kLinkTile = 2048;                   // outputs per workgroup step

@@ -41,7 +41,7 @@ int run(const int16_t *in_dev, uint64_t nin, uint32_t nbefore, const bbb_fir_cfg
     a.nin = nin;
     a.nout = nout;
     a.nbefore = before;
-    a.ngroups = (cfg->ntaps + 7) / 8;
+    a.ngroups = fir_pack_taps(cfg, a.taps);
     a.shift = cfg->shift;
     a.decim = cfg->decim;
     a.phase = cfg->phase;
@@ -49,7 +49,6 @@ int run(const int16_t *in_dev, uint64_t nin, uint32_t nbefore, const bbb_fir_cfg
     a.strict = strict != 0;
     a.in_vec = !((uintptr_t)in_dev & 15);
     a.out_vec = !((uintptr_t)out_dev & 15);
-    for (uint32_t i = 0; i < cfg->ntaps; ++i) a.taps[i / 2] |= (uint32_t)(uint16_t)cfg->taps[i] << (i & 1 ? 0 : 16);
     // decisions of a decimating launch are ORed into the words that two workgroup steps share
     if (mode == 2 && cfg->decim > 1) BBB_HIP(hipMemsetAsync(out_dev, 0, obytes, st));
     return fir_launch(a, mode, std::max(1, cus) * 8, st);
@@ -69,6 +68,12 @@ int bbb::fir_cfg_check(const bbb_fir_cfg *c, bool slice) {
     if (!slice && c->out_bytes != 2 && c->out_bytes != 4)
         return fail(BBB_EINVAL, "out_bytes must be 2 or 4 (got " + std::to_string(c->out_bytes) + ")");
     return BBB_OK;
+}
+
+uint32_t bbb::fir_pack_taps(const bbb_fir_cfg *c, uint32_t words[BBB_FIR_MAX_TAPS / 2]) {
+    std::memset(words, 0, sizeof(uint32_t) * (BBB_FIR_MAX_TAPS / 2));
+    for (uint32_t i = 0; i < c->ntaps; ++i) words[i / 2] |= (uint32_t)(uint16_t)c->taps[i] << (i & 1 ? 0 : 16);
+    return (c->ntaps + 7) / 8;
 }
 
 extern "C" {

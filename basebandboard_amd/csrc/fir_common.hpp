@@ -1,10 +1,11 @@
-// fir_common.hpp -- what the FIR filter (fir_kernels.hip) and the filtered link (link_kernels.hip) share: the LDS image of a
-// workgroup step and the block core that turns it into eight outputs per thread.
+// fir_common.hpp -- what the FIR filter (fir_kernels.hip), the filtered link (link_kernels.hip) and the down-converter
+// (ddc_kernels.hip) share: the LDS image of a workgroup step, the load of a thread's eight input samples, the block core that
+// turns the image into eight outputs per thread and the point core that turns it into one.
 //
 // The image of a step: kFirThreads threads, thread t owns the 8 samples n0 .. n0 + 7, n0 = 8 t, of the step's kFirTile; they
 // are the four dwords from kFirHist / 2 + 4 t on.  The 8 * ngroups samples in front of the step lie below dword kFirHist / 2
 // (thread t < ngroups stores the four dwords from kFirHist / 2 - 4 (t + 1) on).  How the samples get there is the kernel's
-// own business: fir_kernel loads them, link_kernel shapes them.
+// own business: fir_kernel loads them, link_kernel shapes them, ddc_kernel mixes them with its oscillator (two images).
 #pragma once
 
 #include "bbb_common.hpp"
@@ -25,6 +26,24 @@ __device__ __forceinline__ int dot2(uint32_t x, uint32_t h, int acc) {
 }
 
 __device__ __forceinline__ int sat16(int v) { return min(max(v, -32768), 32767); }
+
+// the input samples j0 .. j0 + 7 of a launch structure A (in, nin, nbefore, in_vec) as four dwords; 0 before in[-nbefore]
+// and from in[nin] on.  One 16-byte load where the input is 16-byte aligned and the eight lie inside the record.
+template <class A>
+__device__ __forceinline__ uint4 fir_load8(const A &a, int64_t j0) {
+    const int64_t lo = -(int64_t)a.nbefore, hi = (int64_t)a.nin;
+    if (j0 + 8 <= lo || j0 >= hi) return make_uint4(0, 0, 0, 0);
+    if (a.in_vec && j0 >= lo && j0 + 8 <= hi) return *reinterpret_cast<const uint4 *>(a.in + j0);
+    uint32_t w[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int64_t j = j0 + 2 * k;
+        const uint32_t s0 = j >= lo && j < hi ? (uint16_t)a.in[j] : 0u;
+        const uint32_t s1 = j + 1 >= lo && j + 1 < hi ? (uint16_t)a.in[j + 1] : 0u;
+        w[k] = s0 | s1 << 16;
+    }
+    return make_uint4(w[0], w[1], w[2], w[3]);
+}
 
 // acc[r] = sum_i h[i] x[n0 + r - i] for thread t's outputs n0 + r, r < 8, over the image L and ng groups of four tap words
 // (word p = h[2p + 1] | h[2p] << 16; `taps` is the kernel argument's array, so the words stay scalar loads).  The pairs of
@@ -59,6 +78,34 @@ __device__ __forceinline__ void fir_block8(const uint32_t *L, int t, unsigned ng
         for (int k = 0; k < 4; ++k) d[4 + k] = d[k];
 #pragma unroll
         for (int k = 0; k < 3; ++k) al[4 + k] = al[k];
+    }
+}
+
+// The point core: acc[i] = sum_k h[k] x_i[n - k] of ONE output n over NI images of the same step (x_i: image L[i]), n = l0 + 1 -
+// kFirHist counted from the step's first sample (l0: the image's sample index of the lower sample of pair 0).  Per pair and
+// image one ds_read_b32, one v_alignbyte_b32 whose byte selector (0 or 2) is the parity of l0, and one dot product.  The
+// images' chains are independent, so the reads of one hide behind the dot products of the other.
+template <int NI>
+__device__ __forceinline__ void fir_point(const uint32_t *const (&L)[NI], int l0, int ng, const uint32_t *taps, int (&acc)[NI]) {
+    const int dw = l0 >> 1;
+    const uint32_t sel = (l0 & 1) ? 2u : 0u;
+    uint32_t prev[NI];
+#pragma unroll
+    for (int i = 0; i < NI; ++i) {
+        prev[i] = L[i][dw + 1];
+        acc[i] = 0;
+    }
+    for (int g = 0; g < ng; ++g) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const uint32_t h = taps[4 * g + u];
+#pragma unroll
+            for (int i = 0; i < NI; ++i) {
+                const uint32_t c = L[i][dw - 4 * g - u];
+                acc[i] = dot2(__builtin_amdgcn_alignbyte(prev[i], c, sel), h, acc[i]);
+                prev[i] = c;
+            }
+        }
     }
 }
 

@@ -10,8 +10,7 @@
 //
 // The image and the block core are fir_common.hpp's, shared with the filtered link (link_kernels.hip).
 // Block form (decim = 1): a thread produces the 8 outputs n0 .. n0 + 7, n0 = 8 t, with fir_block8.
-// Point form (decim > 1): a thread produces one requested output at a time; per pair one ds_read_b32, one
-// v_alignbyte_b32 whose byte selector (0 or 2) is the lane's parity, and one dot product.
+// Point form (decim > 1): a thread produces one requested output at a time with fir_point.
 // The slicer writes no samples: the block kernel's 8 decisions are one byte of the packed output, the point kernel takes a
 // ballot of 64 consecutive bits (lane = q mod 64) and stores whole words, or ORs the words a step shares with its neighbour
 // into the zeroed output.
@@ -24,22 +23,6 @@
 namespace bbb {
 namespace {
 
-// the samples j0 .. j0 + 7 as four dwords; 0 before in[-nbefore] and from in[nin] on
-__device__ inline uint4 load8(const FirLaunch &a, int64_t j0) {
-    const int64_t lo = -(int64_t)a.nbefore, hi = (int64_t)a.nin;
-    if (j0 + 8 <= lo || j0 >= hi) return make_uint4(0, 0, 0, 0);
-    if (a.in_vec && j0 >= lo && j0 + 8 <= hi) return *reinterpret_cast<const uint4 *>(a.in + j0);
-    uint32_t w[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int64_t j = j0 + 2 * k;
-        const uint32_t s0 = j >= lo && j < hi ? (uint16_t)a.in[j] : 0u;
-        const uint32_t s1 = j + 1 >= lo && j + 1 < hi ? (uint16_t)a.in[j + 1] : 0u;
-        w[k] = s0 | s1 << 16;
-    }
-    return make_uint4(w[0], w[1], w[2], w[3]);
-}
-
 // MODE 0: int16 out, 1: int32 out, 2: packed decisions.  POINT: the kernel for decim > 1.
 template <int MODE, bool POINT>
 __global__ __launch_bounds__(kFirThreads) void fir_kernel(FirLaunch a) {
@@ -47,8 +30,8 @@ __global__ __launch_bounds__(kFirThreads) void fir_kernel(FirLaunch a) {
     const int t = threadIdx.x;
     const uint64_t nsteps = (a.nin + kFirTile - 1) / kFirTile;
     const int ng = (int)a.ngroups;
-    auto own = [&](uint64_t step) { return load8(a, (int64_t)(step * kFirTile) + 8 * t); };
-    auto lead = [&](uint64_t step) { return t < ng ? load8(a, (int64_t)(step * kFirTile) - 8 * (t + 1)) : make_uint4(0, 0, 0, 0); };
+    auto own = [&](uint64_t step) { return fir_load8(a, (int64_t)(step * kFirTile) + 8 * t); };
+    auto lead = [&](uint64_t step) { return t < ng ? fir_load8(a, (int64_t)(step * kFirTile) - 8 * (t + 1)) : make_uint4(0, 0, 0, 0); };
     uint64_t s = blockIdx.x;
     uint4 cur = make_uint4(0, 0, 0, 0), cur_lead = cur;
     if (s < nsteps) {
@@ -115,21 +98,11 @@ __global__ __launch_bounds__(kFirThreads) void fir_kernel(FirLaunch a) {
             for (uint64_t qb = (q_lo & ~63ull) + (uint64_t)(t - lane); qb < q_hi; qb += kFirThreads) {
                 const uint64_t q = qb + lane;
                 const bool valid = q >= q_lo && q < q_hi;
-                int acc = 0;
-                if (valid) {
-                    const int l0 = (int)(a.phase + q * a.decim - base) + kFirHist - 1;     // the lower sample of pair 0
-                    const int dw = l0 >> 1;
-                    const uint32_t sel = (l0 & 1) ? 2u : 0u;
-                    uint32_t prev = L[dw + 1];
-                    for (int g = 0; g < ng; ++g) {
-#pragma unroll
-                        for (int u = 0; u < 4; ++u) {
-                            const uint32_t c = L[dw - 4 * g - u];
-                            acc = dot2(__builtin_amdgcn_alignbyte(prev, c, sel), a.taps[4 * g + u], acc);
-                            prev = c;
-                        }
-                    }
-                }
+                int acc1[1] = {0};
+                const uint32_t *const img[1] = {L};
+                // l0: the lower sample of pair 0
+                if (valid) fir_point(img, (int)(a.phase + q * a.decim - base) + kFirHist - 1, ng, a.taps, acc1);
+                const int acc = acc1[0];
                 if constexpr (MODE == 2) {
                     const unsigned long long bits = __ballot(valid && eye_decide(acc, a.threshold, a.strict)), mask = __ballot(valid);
                     if (lane == 0 && mask) {

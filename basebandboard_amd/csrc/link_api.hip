@@ -99,9 +99,8 @@ int bbb_link_sweep_open(bbb_lutopt *h, const bbb_tx_cfg *base, const bbb_tx_sett
     s->have_eye = eye != nullptr;
     if (eye) s->eye = *eye;
     s->delay = delay;
-    s->ngroups = (fir->ntaps + 7) / 8;
+    s->ngroups = fir_pack_taps(fir, s->taps);
     s->shift = fir->shift;
-    for (uint32_t i = 0; i < fir->ntaps; ++i) s->taps[i / 2] |= (uint32_t)(uint16_t)fir->taps[i] << (i & 1 ? 0 : 16);
     s->blocks = link_grid_blocks(s->have_eye);
     if (s->blocks < 0) return s->blocks;
 

@@ -10,6 +10,7 @@
 // am(j0 - 1) .. am(j0 + 7) itself, so that no thread waits on another; the look-behind loads hit the cache lines the
 // neighbouring thread has just read.  The state lives in two device slots: a launch reads one and writes the other.
 #include "bbb_common.hpp"
+#include "nco_common.hpp"
 
 namespace bbb {
 namespace {
@@ -18,20 +19,6 @@ constexpr int kPer = 8;                               // samples per thread and 
 constexpr int kStep = kNcoThreads * kPer;             // samples per workgroup and step
 constexpr int kScanTile = kStep * kNcoScanSteps;      // samples per tile of the fm scan
 constexpr uint32_t kMask24 = 0xFFFFFFu;
-
-// The ROM in LDS: kNcoReps replicas of the 1024 int16 entries, replica r at dword r * 513.  Lane l reads replica l % 16,
-// so that lanes whose entries fall on one bank of one replica land on different banks: bank = (r + entry / 2) mod 32.
-// Without replicas, the lanes of a ds_read group (32 lanes) address entries 8 * inc / 2^14 apart, all on one bank at
-// fcw = 2^16 .. 2^17 (16-way); with them no fcw costs more than 2 cycles per group.
-constexpr int kRepWords = 513;
-constexpr int kLdsWords = kNcoReps * kRepWords;
-
-__device__ inline const int16_t *rom_to_lds(const int16_t *rom, uint32_t *lds) {
-    const uint32_t *r32 = reinterpret_cast<const uint32_t *>(rom);
-    for (int i = threadIdx.x; i < kNcoReps * 512; i += blockDim.x) lds[(i >> 9) * kRepWords + (i & 511)] = r32[i & 511];
-    __syncthreads();
-    return reinterpret_cast<const int16_t *>(lds + (threadIdx.x % kNcoReps) * kRepWords);
-}
 
 // 8 consecutive values from p[j0 ..], zero beyond n; one 16-byte load when all 8 exist and the buffers are aligned
 template <typename T>
@@ -121,8 +108,8 @@ __device__ inline void nco_group(const NcoLaunch &a, const int16_t *rom_l, const
 // Constant fm: pa(j) = pa0 + j * inc, exact mod 2^24 in 32-bit arithmetic.  A grid-stride loop over steps of kStep samples.
 template <bool AM, bool PM>
 __global__ __launch_bounds__(kNcoThreads) void nco_const_kernel(NcoLaunch a) {
-    __shared__ uint32_t lds[kLdsWords];
-    const int16_t *rom_l = rom_to_lds(a.rom, lds);
+    __shared__ uint32_t lds[kNcoLdsWords];
+    const int16_t *rom_l = nco_rom_to_lds(a.rom, lds);
     const bbb_nco_state s0 = *a.in;
     const uint32_t inc = a.fcw + (uint32_t)a.fm_c;
     const uint64_t nsteps = (a.n + kStep - 1) / kStep;
@@ -199,9 +186,9 @@ __global__ __launch_bounds__(kScanThreads) void nco_tile_scan_kernel(NcoLaunch a
 // workgroup from the tile's offset, and writes x.
 template <bool AM, bool PM>
 __global__ __launch_bounds__(kNcoThreads) void nco_scan_kernel(NcoLaunch a, uint32_t ntiles) {
-    __shared__ uint32_t lds[kLdsWords];
+    __shared__ uint32_t lds[kNcoLdsWords];
     __shared__ uint32_t wsum[2][kNcoThreads / kWave];
-    const int16_t *rom_l = rom_to_lds(a.rom, lds);
+    const int16_t *rom_l = nco_rom_to_lds(a.rom, lds);
     const bbb_nco_state s0 = *a.in;
     const int lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
     int par = 0;

@@ -189,6 +189,13 @@ class NCO:
         from .spectrum import psd
         return psd(self.acf(nsamples, nlags, chunk_samples), int(nsamples), **psd_kw)
 
+    def ddc(self, taps, decim=1, phase=0, shift=0):
+        """The down-converter of this oscillator's own output (ddc.DDC at its fcw): pa0 = (-3 fcw) mod 2^24 undoes the
+        module's latency of 3, so that the converter's phase at sample t is the phase x(t) was made from when the waveform
+        started at reset.  `taps`: a list of int16 with `shift`, or a fir.FIR."""
+        from .ddc import DDC
+        return DDC(self.fcw, taps, decim, phase, shift, pa0=(-3 * self.fcw) % (1 << 24), device=self.device)
+
     def close(self):
         o, self._o = getattr(self, "_o", None), None
         if o:

@@ -16,6 +16,11 @@
 //                       setting and phase (bits decided, errors) after a header line
 //          nco:         --nco FILE [--fcw 1048576] [--am 16384] [--nco-samples 1e6]   the NCO's tone (bbb_nco_*), written as
 //                       little-endian int16 samples (software/memdump's `<h` format)
+//          ddc:         --ddc 1 [--fcw 1048576] [--am 16384] [--pm 100] [--nco-samples 1e6]   the receive half of the NCO
+//                       (bbb_ddc_run): the tone made with the constant phase offset `pm` (in 1/1024 turn) is taken back to
+//                       baseband by a converter at the same fcw with pa0 = -3 fcw, a 64-tap boxcar at decim 64, polar outputs:
+//                       one JSON line with the range of the magnitude (about am / 4) and of the phase (1/65536 turn: about 64 pm - 16384,
+//                       the tone being a sine and the converter's reference a cosine)
 //          sinc:        --sinc FILE [--eye-samples 1e6] [--prbs 31] [--nv 8] [--shape 16] [--shift 4]   the scope's 16x sinc
 //                       interpolator (bbb_sinc_*; gateware/bbb/sinc.py): one JSON line with the module's 1024 outputs for the
 //                       7-cycle sine of the reference's test, then the eye of a capture at 4 samples per bit (every second
@@ -198,7 +203,7 @@ int main(int argc, char **argv) {
     bool lags_set = false;
     int shape = 16, eye_shift = 4;
     double eye_samples = 1e6;
-    int tx_sweep = 0, nv_lo = 0, nv_hi = 15, fir = 0, link = 0, link_delay = 2, errstat = 0, xcorr = 0;
+    int tx_sweep = 0, nv_lo = 0, nv_hi = 15, fir = 0, link = 0, link_delay = 2, errstat = 0, xcorr = 0, ddc = 0, nco_pm = 100;
     unsigned long errstat_guard = 64;
     unsigned long long init0 = 1;
     double bits = 1e9, from = 0, to = 10, step = 1, loopback = 0, nsamples = 0, grng_eval = 0;
@@ -249,6 +254,8 @@ int main(int argc, char **argv) {
         else if (a == "--delay") link_delay = std::atoi(v);
         else if (a == "--errstat") errstat = std::atoi(v);
         else if (a == "--xcorr") xcorr = std::atoi(v);
+        else if (a == "--ddc") ddc = std::atoi(v);
+        else if (a == "--pm") nco_pm = std::atoi(v);
         else if (a == "--guard") errstat_guard = std::strtoul(v, nullptr, 0);
         else if (a == "--nv-range") {
             if (std::sscanf(v, "%d:%d", &nv_lo, &nv_hi) != 2) { std::fprintf(stderr, "--nv-range A:B\n"); return 2; }
@@ -300,6 +307,54 @@ int main(int argc, char **argv) {
         std::fclose(f);
         std::printf("{\"mode\": \"nco\", \"samples\": %llu, \"fcw\": %lu, \"am\": %lu, \"pa\": %u, \"q\": %d, \"w\": %d, \"y\": %d, "
                     "\"seconds\": %.6f}\n", (unsigned long long)n, nco_fcw, nco_am, st.pa, st.q, st.w, st.y, dt);
+        return 0;
+    }
+
+    // ---- the digital down-converter on the NCO's own tone: amplitude and phase come back ------------------------------------------
+    if (ddc) {
+        if (nco_samples < 128 || nco_samples > 4e9 || nco_fcw >= (1ul << 24) || nco_am >= (1ul << 16) || nco_pm < -512 || nco_pm >= 512) {
+            std::fprintf(stderr, "--nco-samples 128..4e9, --fcw < 2^24, --am < 2^16, --pm in [-512, 512)\n");
+            return 2;
+        }
+        const uint64_t n = (uint64_t)nco_samples;
+        const bbb_nco_cfg cfg = {(uint32_t)nco_fcw, (uint32_t)nco_am, 0, nco_pm};
+        bbb_nco *o = nullptr;
+        int16_t *x = nullptr;
+        uint32_t *pol = nullptr;                                           // (mag: uint16, phase: int16) per output
+        CHECK(bbb_nco_open(&cfg, 0, nullptr, &o));
+        bbb_fir_cfg fc{};
+        fc.ntaps = 64;
+        for (int i = 0; i < 64; ++i) fc.taps[i] = 1;
+        fc.shift = 6, fc.decim = 64, fc.phase = 63;
+        const bbb_ddc_cfg dc = {(uint32_t)nco_fcw, (uint32_t)((0x1000000ul - 3 * nco_fcw % 0x1000000ul) & 0xFFFFFFul), BBB_DDC_POLAR};
+        const uint64_t nout_max = n / 64 + 1;
+        if (hipMalloc((void **)&x, n * sizeof(int16_t)) != hipSuccess || hipMalloc((void **)&pol, nout_max * 4) != hipSuccess) {
+            std::fprintf(stderr, "hipMalloc failed\n");
+            return 1;
+        }
+        uint64_t nout = 0;
+        const double t0 = now_s();
+        CHECK(bbb_nco_run(o, nullptr, nullptr, nullptr, n, x));
+        CHECK(bbb_ddc_run(x, n, 0, 0, &dc, &fc, pol, &nout, 0, nullptr));
+        if (hipDeviceSynchronize() != hipSuccess) { std::fprintf(stderr, "hipDeviceSynchronize failed\n"); return 1; }
+        const double dt = now_s() - t0;
+        std::vector<uint32_t> h(nout);
+        if (hipMemcpy(h.data(), pol, nout * 4, hipMemcpyDeviceToHost) != hipSuccess) { std::fprintf(stderr, "copy failed\n"); return 1; }
+        (void)hipFree(x);
+        (void)hipFree(pol);
+        CHECK(bbb_nco_close(o));
+        // output 0 still holds the oscillator's three samples of latency; the rest is the steady tone
+        unsigned mag_lo = 65535, mag_hi = 0;
+        int ph_lo = 32767, ph_hi = -32768;
+        for (uint64_t q = 1; q < nout; ++q) {
+            const unsigned m = h[q] & 0xFFFFu;
+            const int ph = (int16_t)(h[q] >> 16);
+            mag_lo = m < mag_lo ? m : mag_lo, mag_hi = m > mag_hi ? m : mag_hi;
+            ph_lo = ph < ph_lo ? ph : ph_lo, ph_hi = ph > ph_hi ? ph : ph_hi;
+        }
+        std::printf("{\"mode\": \"ddc\", \"samples\": %llu, \"outputs\": %llu, \"fcw\": %lu, \"am\": %lu, \"pm\": %d, \"mag_min\": %u, "
+                    "\"mag_max\": %u, \"phase_min\": %d, \"phase_max\": %d, \"seconds\": %.6f}\n", (unsigned long long)n,
+                    (unsigned long long)nout, nco_fcw, nco_am, nco_pm, mag_lo, mag_hi, ph_lo, ph_hi, dt);
         return 0;
     }
 

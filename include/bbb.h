@@ -682,6 +682,42 @@ int bbb_fir_filter(const int16_t *in_dev, uint64_t nin, uint32_t nbefore, const 
 int bbb_fir_slice(const int16_t *in_dev, uint64_t nin, uint32_t nbefore, const bbb_fir_cfg *cfg, int32_t threshold,
                   int strict, uint64_t *bits_packed_dev, uint64_t *nbits_out, int device, void *hip_stream);
 
+/* ---- digital down-converter: quadrature mixer, FIR, I/Q or polar outputs (the receive half of gateware/bbb/nco.py) ---- */
+
+/* An int16 capture at a carrier taken to baseband.  All integers, >> arithmetic, rom = bbb_nco_rom:
+ *   j(n)   = (first_sample + n) mod 2^24               n < 0 (history) in two's complement
+ *   pa(n)  = (pa0 + j(n) * fcw) mod 2^24               adr(n) = pa(n) >> 14
+ *   c(n)   = rom[(adr(n) + 256) mod 1024]              s(n) = rom[adr(n)]
+ *   mi(n)  = (x(n) * c(n)) >> 15                       mq(n) = (x(n) * -s(n)) >> 15          both in [-32767, 32767]
+ *   x(n), n < 0: in_dev[n] while n >= -nbefore, 0 beyond (bbb_fir_filter's history rule)
+ *   ai(n)  = sum_{i < ntaps} h[i] * mi(n - i)          aq(n) likewise: exact int32 under the rules of bbb_fir_cfg
+ *   I[q]   = sat16(ai(phase + q * decim) >> shift)     Q[q] likewise; nout as in bbb_fir_cfg
+ * The oscillator has no state: it is a function of the absolute sample number, so a capture cut anywhere and continued with
+ * nbefore / first_sample gives the outputs of one call.  pa0 = (-3 * fcw) mod 2^24 lines it up with a bbb_nco of the same fcw
+ * run from reset (whose output lags its phase accumulator by 3 samples).
+ * mode BBB_DDC_IQ16: out_dev[q] = (I, Q) as two int16 (4-byte aligned).  BBB_DDC_IQ32: (ai >> shift, aq >> shift) as two
+ * int32, unsaturated (8-byte aligned).  BBB_DDC_POLAR: (mag: uint16, phase: int16 in 1/65536 turn) of the IQ16 pair
+ * (4-byte aligned), by this CORDIC: (0, 0) gives (0, 0); otherwise, with neg = I < 0,
+ *   X = (neg ? -I : I) << 14   Y = (neg ? -Q : Q) << 14   Z = neg ? 2^31 : 0 (mod 2^32)
+ *   k = 0..15: d = Y >= 0; (X, Y) = d ? (X + (Y >> k), Y - (X >> k)) : (X - (Y >> k), Y + (X >> k)); Z += d ? A[k] : -A[k]
+ *   A[k] = round(atan(2^-k) / (2 pi) * 2^32)
+ *   mag = (int64(X) * 39797 + 2^29) >> 30            phase = int16(((Z + 2^15) >> 16) mod 2^16)
+ * in int32 (|X|, |Y| < 2^31 for every pair); mag <= 46341 is within 0.59 of hypot, phase within 1 unit of atan2. */
+#define BBB_DDC_IQ16  0
+#define BBB_DDC_IQ32  1
+#define BBB_DDC_POLAR 2
+typedef struct { uint32_t fcw; uint32_t pa0; uint32_t mode; /* BBB_DDC_IQ16 | IQ32 | POLAR */ } bbb_ddc_cfg;
+/* out_dev[q] for q in [0, nout); *nout_out (host, may be NULL) receives nout.  in_dev as in bbb_fir_filter (any 2-byte
+ * alignment; 16-byte aligned takes the wide loads), out_dev aligned to its element (16 bytes: the wide stores of decim 1).
+ * BBB_EINVAL before the device is touched: nulls, fcw or pa0 >= 2^24, a mode that is none of the three, every rule of
+ * bbb_fir_cfg but out_bytes (ignored), first_sample + nin > 2^58, an out_dev that overlaps the samples read.  nin = 0 is a
+ * no-op.  Asynchronous on hip_stream; a device without gfx950 gives BBB_ENODEV. */
+int bbb_ddc_run(const int16_t *in_dev, uint64_t nin, uint32_t nbefore, uint64_t first_sample,
+                const bbb_ddc_cfg *ddc, const bbb_fir_cfg *fir /* out_bytes ignored */,
+                void *out_dev, uint64_t *nout_out, int device, void *hip_stream);
+/* The CORDIC of BBB_DDC_POLAR for one pair (host only, works without a GPU). */
+int bbb_ddc_polar_host(int16_t i, int16_t q, uint16_t *mag, int16_t *phase);
+
 /* ---- the filtered link: eye, bathtub and BER sweep behind a receive filter (rx.py:24-26) -------------------------------- */
 
 /* What bbb_tx_eye_run and bbb_tx_ber_sweep_run give for the raw sample, for the sample AFTER the receive filter, the
