@@ -292,3 +292,27 @@ def check(rc, what):
     if rc == BBB_EINVAL:
         raise ValueError(detail or name)          # e.g. "k=8 invalid for PRBS" (prbs.py:29-30)
     raise BbbError(rc, f"{what} failed ({name})", detail)
+
+
+class Handle:
+    """Base of a class that owns an object of the C ABI: attribute `_handle` holds the raw pointer, the C function `_close`
+    releases it.  close() (once; later calls do nothing), context manager, and a last close when collected."""
+    _handle = _close = None
+
+    def close(self):
+        p = getattr(self, self._handle, None)
+        setattr(self, self._handle, None)
+        if p:
+            check(getattr(lib(), self._close)(p), self._close)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -1,9 +1,7 @@
 // acf_api.hip -- the extern "C" entry points of the autocorrelation counters (include/bbb.h).  Host logic only: argument
-// checks, the transmitter side's chunk loop and its scratch.  Like eye_api.hip, it uses a handle only through public calls
-// (bbb_tx_fill_i16, bbb_awgn_prefetch) and the accessors of bbb_common.hpp, so bbb_api.hip's scheduler model is unchanged.
-#include "bbb_common.hpp"
+// checks and, on the transmitter side, what a chunk of tx_chunks.hpp's loop does and its scratch.
+#include "tx_chunks.hpp"
 
-#include <algorithm>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -53,20 +51,11 @@ hipMemPool_t scratch_pool(int device) {
 }  // namespace
 
 struct bbb_tx_acf {
-    bbb_lutopt *h = nullptr;
-    bbb_tx_cfg cfg{};
     uint32_t nlags = 0;
-    uint64_t chunk = 0;
-    int device = 0;
     AcfPlan plan{};
-    int16_t *buf = nullptr;          // the chunk's waveform and the nlags - 1 (and up to 15 more) samples after it
-    uint64_t *scratch = nullptr;     // per-workgroup partial counters
-
-    ~bbb_tx_acf() {
-        if (device >= 0) (void)hipSetDevice(device);
-        if (buf) (void)hipFree(buf);
-        if (scratch) (void)hipFree(scratch);
-    }
+    DevBuf<uint64_t> scratch;        // per-workgroup partial counters
+    DevBuf<int16_t> buf;             // the chunk's waveform and the nlags - 1 (and up to 15 more) samples after it
+    TxChunks tx;
 };
 
 extern "C" {
@@ -97,25 +86,16 @@ int bbb_acf_accumulate_i16(const int16_t *samples_dev, uint64_t nfirst, uint64_t
 }
 
 int bbb_tx_acf_open(bbb_lutopt *h, const bbb_tx_cfg *cfg, uint32_t nlags, uint64_t chunk_samples, bbb_tx_acf **out) {
-    if (!h) return fail(BBB_EINVAL, "null handle");
-    if (!out) return fail(BBB_EINVAL, "null out");
-    int rc = tx_cfg_check(cfg);
-    if (rc) return rc;
-    if ((rc = lags_check(nlags))) return rc;
-    if (chunk_samples > kAcfChunkMax) return fail(BBB_EINVAL, "chunk_samples must be <= 2^30");
-    const int device = lutopt_device(h);
-    if (device < 0) return fail(BBB_ENODEV, "host-only handle (device -1) cannot generate samples");
-    if ((rc = use_device(device))) return rc;
     auto a = std::make_unique<bbb_tx_acf>();
-    a->h = h;
-    a->cfg = *cfg;
+    int rc = tx_chunks_open(&a->tx, h, out, cfg, chunk_samples, kAcfChunkDefault, kAcfChunkMax, [&] {
+        const int bad = tx_cfg_check(cfg);
+        return bad ? bad : lags_check(nlags);
+    });
+    if (rc) return rc;
     a->nlags = nlags;
-    a->device = device;
-    a->chunk = chunk_samples ? chunk_samples : kAcfChunkDefault;
-    a->plan = acf_plan(nlags, a->chunk);
+    a->plan = acf_plan(nlags, a->tx.chunk);
     if (a->plan.gx < 0) return fail(BBB_EHIP, "could not size the correlator's grid");
-    BBB_HIP(hipMalloc((void **)&a->buf, fill_len(a->chunk, nlags) * sizeof(int16_t)));
-    BBB_HIP(hipMalloc((void **)&a->scratch, a->plan.scratch_words * sizeof(uint64_t)));
+    if ((rc = a->buf.grow(fill_len(a->tx.chunk, nlags))) || (rc = a->scratch.grow(a->plan.scratch_words))) return rc;
     *out = a.release();
     return BBB_OK;
 }
@@ -126,24 +106,11 @@ int bbb_tx_acf_run(bbb_tx_acf *a, uint64_t first_sample, uint64_t nsamples, int6
     if ((uintptr_t)acf_dev & 7) return fail(BBB_EINVAL, "misaligned device pointer");
     if (first_sample > kAcfSampleLimit - a->nlags - 16 || nsamples > kAcfSampleLimit - a->nlags - 16 - first_sample)
         return fail(BBB_EINVAL, "first_sample + nsamples + nlags + 16 must be <= 2^62");
-    if (nsamples == 0) return BBB_OK;
-    BBB_HIP(hipSetDevice(a->device));
-    const uint64_t look = a->nlags - 1;
-    int rc;
-    for (uint64_t off = 0; off < nsamples;) {
-        const uint64_t n = std::min(a->chunk, nsamples - off), s = first_sample + off;
-        if ((rc = bbb_tx_fill_i16(a->h, &a->cfg, a->buf, fill_len(n, a->nlags), s))) return rc;
-        // announce the next chunk's fill, as bbb_tx_eye_run does: its noise start states are derived beside this chunk
-        if (a->cfg.noise_en && off + n < nsamples &&
-            (rc = bbb_awgn_prefetch(a->h, fill_len(std::min(a->chunk, nsamples - off - n), a->nlags), a->cfg.warmup + s + n)))
-            return rc;
-        hipStream_t st = lutopt_stream(a->h);     // the handle's stream, read per chunk like the fill itself does
-        BBB_HIP(hipSetDevice(a->device));
-        if ((rc = acf_launch(a->plan, a->buf, n, n + look, a->nlags, a->scratch, reinterpret_cast<uint64_t *>(acf_dev), st)))
-            return rc;
-        off += n;
-    }
-    return BBB_OK;
+    // a chunk of n first elements fills (and the chunk before it announces) the samples behind it that its lags reach
+    const auto padded = [&](uint64_t first, uint64_t n) { return TxRange{first, fill_len(n, a->nlags)}; };
+    return tx_chunks_walk(a->tx, a->buf.p, first_sample, nsamples, padded, [&](uint64_t, uint64_t n, hipStream_t st) {
+        return acf_launch(a->plan, a->buf, n, n + a->nlags - 1, a->nlags, a->scratch, reinterpret_cast<uint64_t *>(acf_dev), st);
+    });
 }
 
 int bbb_tx_acf_close(bbb_tx_acf *a) {

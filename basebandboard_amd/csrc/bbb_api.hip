@@ -1,6 +1,7 @@
 // bbb_api.hip -- the extern "C" boundary of libbbb_hip.so (see include/bbb.h).
 // Host logic only: argument checks, GF(2) jump-ahead plans, workspace, kernel launches.
 #include "bbb_common.hpp"
+#include "dev_buf.hpp"
 #include "awgn_launch.hpp"
 #include "stage_common.hpp"
 #include "gf2.hpp"
@@ -52,29 +53,6 @@ int use_device(int device) {
 }
 
 namespace {
-
-// A device buffer of T (Pinned: page-locked host memory) that grows to exactly the size asked for: the old buffer is freed
-// first, nothing is allocated ahead.  hipFree waits for the device, so a grow is a host synchronisation.  Move-only; the
-// destructor frees it.
-template <typename T, bool Pinned = false>
-struct DevBuf {
-    T *p = nullptr;
-    size_t cap = 0;
-    DevBuf() = default;
-    DevBuf(DevBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
-    DevBuf &operator=(DevBuf &&o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); return *this; }   // (o frees the old one)
-    ~DevBuf() { if (p) (void)(Pinned ? hipHostFree(p) : hipFree(p)); }
-    operator T *() const { return p; }
-    int grow(size_t need) {
-        if (cap >= need) return BBB_OK;
-        if (p) BBB_HIP(Pinned ? hipHostFree(p) : hipFree(p));
-        p = nullptr;
-        cap = 0;
-        BBB_HIP(Pinned ? hipHostMalloc((void **)&p, need * sizeof(T), hipHostMallocDefault) : hipMalloc((void **)&p, need * sizeof(T)));
-        cap = need;
-        return BBB_OK;
-    }
-};
 
 // A hipEventDisableTiming event, created by its first record (a host-only handle creates none); the destructor destroys it.
 struct Event {

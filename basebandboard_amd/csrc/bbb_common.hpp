@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -34,8 +35,12 @@ int use_device(int device);
 
 constexpr int kWave = 64;   // CDNA wavefront
 
-// floor(v / 8) for signed v
-inline int64_t floor8(int64_t v) { return v >= 0 ? v / 8 : -((-v + 7) / 8); }
+// floor(v / d) for signed v and d > 0
+inline int64_t floor_div(int64_t v, int64_t d) { return v >= 0 ? v / d : -((-v + d - 1) / d); }
+inline int64_t floor8(int64_t v) { return floor_div(v, 8); }
+
+// data bits lo .. hi (inclusive; lo may lie below bit 0, hi < lo: none) that a chunk of samples needs
+struct BitRange { int64_t lo, hi; };
 
 // the transmitter's own range, for every call that takes first_sample and nsamples
 inline int tx_range_check(uint64_t first, uint64_t n) {
@@ -89,6 +94,12 @@ int eye_cfg_check(const bbb_eye_cfg *eye);        // eye_api.hip: the rules of b
 inline uint64_t eye_scratch_words(int blocks, uint32_t ncols) { return (uint64_t)blocks * (256u * ncols + 8u); }
 int eye_accumulate_launch(const EyeLaunch &a, const int16_t *samples, uint64_t nsamples, uint64_t first_sample,
                           uint32_t *scratch, int blocks, uint64_t *hist, uint64_t *bathtub, hipStream_t st);
+// the bits whose eight phase samples 8m + BBB_TX_BIT_SAMPLE0 + p meet samples [first, first + n), and the u64 words that hold
+// those of any chunk of up to `chunk` samples: at most chunk / 8 + 1 bits
+inline BitRange eye_bit_range(uint64_t first, uint64_t n) {
+    return {floor8((int64_t)first - BBB_TX_BIT_SAMPLE0), floor8((int64_t)(first + n - 1) - BBB_TX_BIT_SAMPLE0)};
+}
+inline uint64_t eye_bits_words(uint64_t chunk) { return (chunk / 8 + 2) / 64 + 3; }
 
 // txsweep_kernels.hip: the BER sweep over transmitter settings (include/bbb.h, bbb_tx_ber_sweep_*)
 constexpr int kSweepMaxPairs = 8;                 // settings per launch: two per packed 16-bit lane operation
@@ -114,6 +125,12 @@ int sweep_grid_blocks(uint64_t n);
 inline uint64_t sweep_scratch_words(int blocks) { return (uint64_t)blocks * (2 * kSweepMaxPairs * 8); }
 int sweep_launch(const SweepGroup &g, const uint16_t *tables, const SweepChunk &c, uint32_t *scratch, int blocks,
                  uint64_t *counters, hipStream_t st);
+// sample n needs the shaper window, bits M-7 .. M with M = floor((n - 17) / 8), and the window of a chunk's last thread reads
+// 2 more: at most chunk / 8 + 10 bits
+inline BitRange sweep_bit_range(uint64_t first, uint64_t n) {
+    return {floor8((int64_t)first - 17) - 7, floor8((int64_t)(first + n - 1) - 17) + 2};
+}
+inline uint64_t sweep_bits_words(uint64_t chunk) { return (chunk / 8 + 16) / 64 + 2; }
 
 // acf_kernels.hip: the autocorrelation counters (include/bbb.h, bbb_acf_accumulate_i16 / bbb_tx_acf_*)
 struct AcfPlan {
@@ -225,6 +242,13 @@ int link_grid_blocks(bool hist);
 // counters[8][2] and hist[256][ncols] += what stream samples [first, first + n) of the launch give; either may be nullptr
 int link_launch(const LinkLaunch &a, bool hist, uint64_t first, uint64_t n, uint32_t *scratch, int blocks, uint64_t *hist_out,
                 uint64_t *counters, hipStream_t st);
+// a launch whose first tile starts at tb and whose filter reaches `lead` samples back, with outputs up to out_hi: a thread
+// looks at the 10 bits of its shaper window and up to 47 bits below them, where the decided bits lie.  One of the words is
+// slack behind the last bit (LinkLaunch::nwords, all readable).
+inline BitRange link_bit_range(int64_t tb, int64_t lead, int64_t out_hi) {
+    return {floor8(std::max<int64_t>(0, tb - lead) - 17) - 47, floor8(out_hi - 1 - 17) + 2};
+}
+inline uint64_t link_bits_words(uint64_t chunk) { return (chunk / 8 + 160) / 64 + 4; }
 
 // bbb_api.hip: what the eye object needs of a handle (reads fields only) and the bbb_tx_cfg checks of bbb_tx_fill_i16
 int lutopt_device(const bbb_lutopt *h);
@@ -286,5 +310,12 @@ XcorrPlan xcorr_plan(uint32_t spb, uint32_t nlags, uint64_t max_nsamples);
 int xcorr_launch(const XcorrPlan &p, const XcorrLaunch &l, uint64_t *scratch, int64_t *xc, hipStream_t st);
 // the Pulser's data bits first_bit .. first_bit + 64 nwords - 1, packed as bbb_prbs_fill packs
 int xcorr_pulser_bits_launch(uint64_t *dst, uint64_t first_bit, uint64_t nwords, hipStream_t st);
+// the data bits samples [first, first + n) need, n > 0, already clamped at bit 0 (the capture side compares against them);
+// the words of a transmitter chunk (spb 8): at most (chunk + nlags - 1) / 8 + 2 bits
+inline BitRange xcorr_bit_range(uint64_t first, uint64_t n, const bbb_xcorr_cfg &c) {
+    const int64_t f = (int64_t)first - (int64_t)c.origin;
+    return {std::max<int64_t>(0, floor_div(f - (int64_t)(c.nlags - 1), c.spb)), floor_div(f + (int64_t)n - 1, c.spb)};
+}
+inline uint64_t xcorr_bits_words(uint64_t chunk, uint32_t nlags) { return ((chunk + nlags) / 8 + 2) / 64 + 3; }
 
 }  // namespace bbb

@@ -1,10 +1,7 @@
 // eye_api.hip -- the extern "C" entry points of the eye diagram and bathtub (include/bbb.h).  Host logic only: argument
-// checks, the transmitter side's chunk loop and its scratch.  Kept out of bbb_api.hip, whose scheduler is compiled unchanged
-// against a model of HIP (tests/sched_model/): the eye object uses the handle only through public calls (bbb_tx_fill_i16,
-// bbb_awgn_prefetch) and two accessors that read its device and stream.
-#include "bbb_common.hpp"
+// checks and, on the transmitter side, what a chunk of tx_chunks.hpp's loop does and its scratch.
+#include "tx_chunks.hpp"
 
-#include <algorithm>
 #include <memory>
 #include <string>
 
@@ -36,22 +33,12 @@ int bbb::eye_cfg_check(const bbb_eye_cfg *eye) {
 }
 
 struct bbb_tx_eye {
-    bbb_lutopt *h = nullptr;
-    bbb_tx_cfg cfg{};
     bbb_eye_cfg eye{};
-    uint64_t chunk = 0;
-    int device = 0, blocks = 0;
-    int16_t *buf = nullptr;          // the chunk's waveform
-    uint64_t *bits = nullptr;        // the chunk's data bits
-    uint32_t *scratch = nullptr;     // per-block partial histograms
-    uint64_t bits_words = 0;
-
-    ~bbb_tx_eye() {
-        if (device >= 0) (void)hipSetDevice(device);
-        if (buf) (void)hipFree(buf);
-        if (bits) (void)hipFree(bits);
-        if (scratch) (void)hipFree(scratch);
-    }
+    int blocks = 0;
+    DevBuf<uint32_t> scratch;        // per-block partial histograms
+    DevBuf<uint64_t> bits;           // the chunk's data bits
+    DevBuf<int16_t> buf;             // the chunk's waveform
+    TxChunks tx;
 };
 
 extern "C" {
@@ -80,28 +67,18 @@ int bbb_eye_accumulate_i16(const int16_t *samples_dev, uint64_t nsamples, uint64
 }
 
 int bbb_tx_eye_open(bbb_lutopt *h, const bbb_tx_cfg *cfg, const bbb_eye_cfg *eye, uint64_t chunk_samples, bbb_tx_eye **out) {
-    if (!h) return fail(BBB_EINVAL, "null handle");
-    if (!out) return fail(BBB_EINVAL, "null out");
-    int rc = tx_cfg_check(cfg);
-    if (rc) return rc;
-    if ((rc = eye_cfg_check(eye))) return rc;
-    if (chunk_samples > kEyeChunkMax) return fail(BBB_EINVAL, "chunk_samples must be <= 2^30");
-    const int device = lutopt_device(h);
-    if (device < 0) return fail(BBB_ENODEV, "host-only handle (device -1) cannot generate samples");
-    if ((rc = use_device(device))) return rc;
     auto e = std::make_unique<bbb_tx_eye>();
-    e->h = h;
-    e->cfg = *cfg;
+    int rc = tx_chunks_open(&e->tx, h, out, cfg, chunk_samples, kEyeChunkDefault, kEyeChunkMax, [&] {
+        const int bad = tx_cfg_check(cfg);
+        return bad ? bad : eye_cfg_check(eye);
+    });
+    if (rc) return rc;
     e->eye = *eye;
-    e->device = device;
-    e->chunk = chunk_samples ? chunk_samples : kEyeChunkDefault;
-    e->blocks = eye_grid_blocks(e->chunk);
+    e->blocks = eye_grid_blocks(e->tx.chunk);
     if (e->blocks < 0) return e->blocks;
-    // the data bits of a chunk: bits floor((s - 45) / 8) .. floor((s + chunk - 46) / 8), at most chunk / 8 + 1 of them
-    e->bits_words = (e->chunk / 8 + 2) / 64 + 3;
-    BBB_HIP(hipMalloc((void **)&e->buf, ((e->chunk + 7) & ~7ull) * sizeof(int16_t)));
-    BBB_HIP(hipMalloc((void **)&e->bits, e->bits_words * sizeof(uint64_t)));
-    BBB_HIP(hipMalloc((void **)&e->scratch, eye_scratch_words(e->blocks, eye->ncols) * sizeof(uint32_t)));
+    if ((rc = e->buf.grow((e->tx.chunk + 7) & ~7ull)) || (rc = e->bits.grow(eye_bits_words(e->tx.chunk))) ||
+        (rc = e->scratch.grow(eye_scratch_words(e->blocks, eye->ncols))))
+        return rc;
     *out = e.release();
     return BBB_OK;
 }
@@ -110,36 +87,21 @@ int bbb_tx_eye_run(bbb_tx_eye *e, uint64_t first_sample, uint64_t nsamples, uint
     if (!hist_dev && !bathtub_dev) return fail(BBB_EINVAL, "hist_dev and bathtub_dev are both NULL");
     if (!e) return fail(BBB_EINVAL, "null eye object");
     if (((uintptr_t)hist_dev & 7) || ((uintptr_t)bathtub_dev & 7)) return fail(BBB_EINVAL, "misaligned device pointer");
-    int rc = tx_range_check(first_sample, nsamples);
-    if (rc) return rc;
-    if (nsamples == 0) return BBB_OK;
-    BBB_HIP(hipSetDevice(e->device));
+    if (const int rc = tx_range_check(first_sample, nsamples)) return rc;
     EyeLaunch a = launch_of(e->eye);
     a.want_hist = hist_dev != nullptr;
     a.want_tub = bathtub_dev != nullptr;
-    a.pulser = e->cfg.source == 1;
-    for (uint64_t off = 0; off < nsamples;) {
-        const uint64_t n = std::min(e->chunk, nsamples - off), s = first_sample + off;
-        if ((rc = bbb_tx_fill_i16(e->h, &e->cfg, e->buf, n, s))) return rc;
-        // announce the next chunk, as TX.generate does: its noise start states are derived beside this chunk's kernels
-        if (e->cfg.noise_en && off + n < nsamples &&
-            (rc = bbb_awgn_prefetch(e->h, std::min(e->chunk, nsamples - off - n), e->cfg.warmup + s + n)))
-            return rc;
-        hipStream_t st = lutopt_stream(e->h);     // the handle's stream, read per chunk like the fill itself does
-        BBB_HIP(hipSetDevice(e->device));
-        if (a.want_tub && !a.pulser) {
-            const int64_t lo = std::max<int64_t>(0, floor8((int64_t)s - BBB_TX_BIT_SAMPLE0));
-            const int64_t hi = floor8((int64_t)(s + n - 1) - BBB_TX_BIT_SAMPLE0);
-            a.bits = reinterpret_cast<const unsigned long long *>(e->bits);
-            a.bit0 = lo;
-            a.nbits = hi >= lo ? (uint64_t)(hi - lo + 1) : 0;
-            if (a.nbits && (rc = bbb_prbs_fill(e->cfg.prbs_k, e->cfg.prbs_state, (uint64_t)lo, a.nbits, e->bits, e->device, st)))
-                return rc;
+    a.pulser = e->tx.cfg.source == 1;
+    return tx_chunks_walk(e->tx, e->buf.p, first_sample, nsamples, tx_same_range, [&](uint64_t s, uint64_t n, hipStream_t st) {
+        if (a.want_tub && !a.pulser) {             // (the Pulser's bits are computed where they are needed)
+            a.bits = reinterpret_cast<const unsigned long long *>(e->bits.p);
+            TxBits b;
+            if (const int rc = tx_chunk_bits(e->tx, eye_bit_range(s, n), e->bits, e->bits.cap, st, &b)) return rc;
+            a.bit0 = b.lo;
+            a.nbits = b.n;
         }
-        if ((rc = eye_accumulate_launch(a, e->buf, n, s, e->scratch, e->blocks, hist_dev, bathtub_dev, st))) return rc;
-        off += n;
-    }
-    return BBB_OK;
+        return eye_accumulate_launch(a, e->buf, n, s, e->scratch, e->blocks, hist_dev, bathtub_dev, st);
+    });
 }
 
 int bbb_tx_eye_close(bbb_tx_eye *e) {

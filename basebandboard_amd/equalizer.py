@@ -57,16 +57,15 @@ def capture_xcorr(samples, bits, spb, origin, nlags, first_sample=0, bit0=0, xco
     return xcorr
 
 
-class TxXcorr:
+class TxXcorr(_lib.Handle):
     """bbb_tx_xcorr_*: counters of a TX's waveform against its own data bits (its settings copied at open; spb 8, origin
     TX_BIT_ORIGIN), chunk by chunk on the generator's stream.  Context manager; close it before the TX's generator handle
     goes."""
+    _handle, _close = "_x", "bbb_tx_xcorr_close"
 
     def __init__(self, tx, nlags=64, warmup=16, chunk_samples=0):
-        from .bitshaper import _cfg
         self.tx, self.nlags = tx, int(nlags)
-        shaper = tx.pulse_shaper if tx.src_sel else tx.prbs_shaper            # the selection TX.generate uses (tx.py:65)
-        cfg = _cfg(shaper.coefficients[shaper.setsel], shaper.prbs, tx.bit_en, tx.noise_en, tx.noise_var, warmup)
+        cfg = tx._c_cfg(warmup)
         x = C.c_void_p()
         tx.urng._bind_stream()
         _lib.check(_lib.lib().bbb_tx_xcorr_open(tx.urng._h, C.byref(cfg), self.nlags, int(chunk_samples), C.byref(x)),
@@ -81,23 +80,6 @@ class TxXcorr:
         _lib.check(_lib.lib().bbb_tx_xcorr_run(self._x, int(first_sample), int(nsamples), C.c_void_p(xcorr.data_ptr())),
                    "bbb_tx_xcorr_run")
         return xcorr
-
-    def close(self):
-        x, self._x = getattr(self, "_x", None), None
-        if x:
-            _lib.check(_lib.lib().bbb_tx_xcorr_close(x), "bbb_tx_xcorr_close")
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def tx_xcorr(tx, nsamples, first_sample=0, nlags=64, warmup=16, chunk_samples=0, xcorr=None):

@@ -74,15 +74,14 @@ def capture_eye(samples, first_sample=0, eye=None, hist=None):
     return hist
 
 
-class TxEye:
+class TxEye(_lib.Handle):
     """bbb_tx_eye_*: eye and bathtub of a TX's waveform (its settings copied at open), chunk by chunk on the generator's
     stream.  Context manager; close it before the TX's generator handle goes."""
+    _handle, _close = "_e", "bbb_tx_eye_close"
 
     def __init__(self, tx, eye=None, warmup=16, chunk_samples=0):
-        from .bitshaper import _cfg
         self.tx, self.eye = tx, eye or EyeConfig(col_origin=BIT_SAMPLE0)
-        shaper = tx.pulse_shaper if tx.src_sel else tx.prbs_shaper            # the selection TX.generate uses (tx.py:65)
-        cfg = _cfg(shaper.coefficients[shaper.setsel], shaper.prbs, tx.bit_en, tx.noise_en, tx.noise_var, warmup)
+        cfg = tx._c_cfg(warmup)
         ec = self.eye._c()
         e = C.c_void_p()
         tx.urng._bind_stream()
@@ -102,23 +101,6 @@ class TxEye:
                                              C.c_void_p(bathtub.data_ptr() if bathtub is not None else None)),
                    "bbb_tx_eye_run")
         return hist, bathtub
-
-    def close(self):
-        e, self._e = getattr(self, "_e", None), None
-        if e:
-            _lib.check(_lib.lib().bbb_tx_eye_close(e), "bbb_tx_eye_close")
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def tx_eye(tx, nsamples, first_sample=0, warmup=16, eye=None, chunk_samples=0, hist=None, bathtub=None):

@@ -16,20 +16,21 @@ import torch
 
 from . import _lib
 from .eye import ROWS, _counters
-from .txsweep import TxSetting, _c_setting, _shaper
+from .tx import _shaper
+from .txsweep import TxSetting, _c_setting
 
 MAX_DELAY = 255
 
 
-class LinkSweep:
+class LinkSweep(_lib.Handle):
     """bbb_link_sweep_*: bathtub and eye of a TX's waveform behind `rx_filter` (a fir.FIR) for many settings at once, chunk by
     chunk on the generator's stream.  The TX supplies the source, the PRBS and the generator, each txsweep.TxSetting the
     rest (its threshold is in units of acc).  delay None: rx_filter.design_delay where a design set it (FIR.mmse), else rx_filter.delay().  eye: an eye.EyeConfig for histograms of z
     (ncols, shift, col_origin; its threshold / strict are not used).  Context manager; close it before the TX's generator
     handle goes."""
+    _handle, _close = "_s", "bbb_link_sweep_close"
 
     def __init__(self, tx, settings, rx_filter, delay=None, eye=None, warmup=16, chunk_samples=0):
-        from .bitshaper import _cfg
         self.tx, self.eye = tx, eye
         self.settings = list(settings)
         if not self.settings:
@@ -40,8 +41,7 @@ class LinkSweep:
         self.delay = int(delay)
         if not 0 <= self.delay < 1 << 32:
             raise ValueError("delay must be 0..255")
-        sh = _shaper(tx)
-        base = _cfg(sh.coefficients[sh.setsel], sh.prbs, tx.bit_en, tx.noise_en, tx.noise_var, warmup)
+        base = tx._c_cfg(warmup)
         arr = (_lib.TxSetting * len(self.settings))(*[_c_setting(tx, s) for s in self.settings])
         fir = rx_filter._cfg(1, 0)
         ec = eye._c() if eye is not None else None
@@ -68,23 +68,6 @@ class LinkSweep:
                                                  C.c_void_p(hist.data_ptr() if hist is not None else None)),
                    "bbb_link_sweep_run")
         return counters if self.eye is None else (counters, hist)
-
-    def close(self):
-        s, self._s = getattr(self, "_s", None), None
-        if s:
-            _lib.check(_lib.lib().bbb_link_sweep_close(s), "bbb_link_sweep_close")
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def link_eye(tx, nsamples, rx_filter, delay=None, first_sample=0, warmup=16, eye=None, chunk_samples=0, hist=None, bathtub=None):

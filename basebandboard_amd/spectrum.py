@@ -47,15 +47,14 @@ def capture_acf(samples, nlags=256, nfirst=None, acf=None):
     return acf
 
 
-class TxAcf:
+class TxAcf(_lib.Handle):
     """bbb_tx_acf_*: counters of a TX's waveform (its settings copied at open), chunk by chunk on the generator's stream.
     Context manager; close it before the TX's generator handle goes."""
+    _handle, _close = "_a", "bbb_tx_acf_close"
 
     def __init__(self, tx, nlags=256, warmup=16, chunk_samples=0):
-        from .bitshaper import _cfg
         self.tx, self.nlags = tx, int(nlags)
-        shaper = tx.pulse_shaper if tx.src_sel else tx.prbs_shaper            # the selection TX.generate uses (tx.py:65)
-        cfg = _cfg(shaper.coefficients[shaper.setsel], shaper.prbs, tx.bit_en, tx.noise_en, tx.noise_var, warmup)
+        cfg = tx._c_cfg(warmup)
         a = C.c_void_p()
         tx.urng._bind_stream()
         _lib.check(_lib.lib().bbb_tx_acf_open(tx.urng._h, C.byref(cfg), self.nlags, int(chunk_samples), C.byref(a)),
@@ -70,23 +69,6 @@ class TxAcf:
         _lib.check(_lib.lib().bbb_tx_acf_run(self._a, int(first_sample), int(nsamples), C.c_void_p(acf.data_ptr())),
                    "bbb_tx_acf_run")
         return acf
-
-    def close(self):
-        a, self._a = getattr(self, "_a", None), None
-        if a:
-            _lib.check(_lib.lib().bbb_tx_acf_close(a), "bbb_tx_acf_close")
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def tx_acf(tx, nsamples, first_sample=0, nlags=256, warmup=16, chunk_samples=0, acf=None):

@@ -16,6 +16,11 @@ from .prbs import PRBS
 from .rng import CLTGRNG, LUTOPT
 
 
+def _shaper(tx):
+    """The shaper whose output is the waveform (tx.py:65).  The one place where the selection is made."""
+    return tx.pulse_shaper if tx.src_sel else tx.prbs_shaper
+
+
 class TX:
     def __init__(self, prbs_k, bit_en, src_sel, shape_sel, noise_en, noise_var, device=0, init=1, prbs_init=1):
         self.betas = np.linspace(0, 1, 32).tolist()                      # tx.py:54
@@ -30,6 +35,11 @@ class TX:
         self.bit_en, self.src_sel, self.noise_en, self.noise_var = bool(bit_en), int(src_sel), bool(noise_en), int(noise_var)
         self.device = int(device)
 
+    def _c_cfg(self, warmup):
+        """The bbb_tx_cfg of this transmitter: what generate and every analyser of its waveform hand the library."""
+        sh = _shaper(self)
+        return _cfg(sh.coefficients[sh.setsel], sh.prbs, self.bit_en, self.noise_en, self.noise_var, warmup)
+
     def generate(self, nsamples, first_sample=0, warmup=16, out=None, stream_on=True):
         """Samples first_sample .. first_sample + nsamples - 1 of `x` (int16, 12-bit signed).
         stream_on: announce that the next call continues where this one ends (bbb_awgn_prefetch), so that the
@@ -40,8 +50,7 @@ class TX:
             out = torch.empty(int(nsamples), dtype=torch.int16, device=dev)
         if out.dtype != torch.int16 or out.numel() < nsamples or not out.is_contiguous() or out.device != dev:
             raise ValueError(f"out must be a contiguous int16 tensor on {dev} with >= nsamples elements")
-        shaper = self.pulse_shaper if self.src_sel else self.prbs_shaper            # tx.py:65
-        cfg = _cfg(shaper.coefficients[shaper.setsel], shaper.prbs, self.bit_en, self.noise_en, self.noise_var, warmup)
+        cfg = self._c_cfg(warmup)
         self.urng._bind_stream()
         _lib.check(_lib.lib().bbb_tx_fill_i16(self.urng._h, C.byref(cfg), C.c_void_p(out.data_ptr()), int(nsamples),
                                               int(first_sample)), "bbb_tx_fill_i16")
@@ -105,15 +114,15 @@ class TX:
         return WaveformStream(self, nsamples_per_call, first_sample, warmup)
 
 
-class WaveformStream:
+class WaveformStream(_lib.Handle):
     """bbb_tx_stream_*: the transmitter's waveform read sequentially in equal calls; the library turns the two-kernel
     form on and announces every next call.  The TX object's settings are copied when the stream is opened.  Context
     manager; closing restores the generator handle's mode."""
+    _handle, _close = "_s", "bbb_tx_stream_close"
 
     def __init__(self, tx, nsamples_per_call, first_sample=0, warmup=16):
         self.tx, self.n = tx, int(nsamples_per_call)
-        shaper = tx.pulse_shaper if tx.src_sel else tx.prbs_shaper            # tx.py:65
-        cfg = _cfg(shaper.coefficients[shaper.setsel], shaper.prbs, tx.bit_en, tx.noise_en, tx.noise_var, warmup)
+        cfg = tx._c_cfg(warmup)
         s = C.c_void_p()
         tx.urng._bind_stream()
         _lib.check(_lib.lib().bbb_tx_stream_open(tx.urng._h, C.byref(cfg), self.n, int(first_sample), C.byref(s)), "bbb_tx_stream_open")
@@ -147,19 +156,3 @@ class WaveformStream:
         _lib.check(_lib.lib().bbb_tx_stream_tell(self._s, C.byref(v)), "bbb_tx_stream_tell")
         return v.value
 
-    def close(self):
-        s, self._s = getattr(self, "_s", None), None
-        if s:
-            _lib.check(_lib.lib().bbb_tx_stream_close(s), "bbb_tx_stream_close")
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

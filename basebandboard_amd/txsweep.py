@@ -14,6 +14,7 @@ import torch
 
 from . import _lib
 from .eye import _counters
+from .tx import _shaper
 
 
 @dataclass
@@ -27,10 +28,6 @@ class TxSetting:
     threshold: int = 0
     strict: bool = False
     coeffs: Optional[Sequence[int]] = None
-
-
-def _shaper(tx):
-    return tx.pulse_shaper if tx.src_sel else tx.prbs_shaper                   # the selection TX.generate uses (tx.py:65)
 
 
 def _c_setting(tx, s):
@@ -51,19 +48,18 @@ def _c_setting(tx, s):
     return c
 
 
-class TxBerSweep:
+class TxBerSweep(_lib.Handle):
     """bbb_tx_ber_sweep_*: the bathtub of a TX's waveform for many settings at once, chunk by chunk on the generator's
     stream.  The TX supplies the source (PRBS or Pulser, tx.src_sel), the PRBS and the generator; each setting supplies the
     rest.  Context manager; close it before the TX's generator handle goes."""
+    _handle, _close = "_s", "bbb_tx_ber_sweep_close"
 
     def __init__(self, tx, settings, warmup=16, chunk_samples=0):
-        from .bitshaper import _cfg
         self.tx = tx
         self.settings = list(settings)
         if not self.settings:
             raise ValueError("at least one setting")
-        sh = _shaper(tx)
-        base = _cfg(sh.coefficients[sh.setsel], sh.prbs, tx.bit_en, tx.noise_en, tx.noise_var, warmup)
+        base = tx._c_cfg(warmup)
         arr = (_lib.TxSetting * len(self.settings))(*[_c_setting(tx, s) for s in self.settings])
         h = C.c_void_p()
         tx.urng._bind_stream()
@@ -80,23 +76,6 @@ class TxBerSweep:
         _lib.check(_lib.lib().bbb_tx_ber_sweep_run(self._s, int(first_sample), int(nsamples), C.c_void_p(counters.data_ptr())),
                    "bbb_tx_ber_sweep_run")
         return counters
-
-    def close(self):
-        s, self._s = getattr(self, "_s", None), None
-        if s:
-            _lib.check(_lib.lib().bbb_tx_ber_sweep_close(s), "bbb_tx_ber_sweep_close")
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def tx_ber_sweep(tx, nsamples, noise_vars=range(16), shape_sels=None, threshold=0, strict=False, first_sample=0, warmup=16,

@@ -18,6 +18,10 @@ enum hipMemcpyKind { hipMemcpyHostToHost = 0, hipMemcpyHostToDevice = 1, hipMemc
 enum { hipEventDisableTiming = 2, hipStreamNonBlocking = 1, hipHostMallocDefault = 0 };
 struct hipDeviceProp_t { char gcnArchName[256]; int multiProcessorCount; };
 enum hipDeviceAttribute_t { hipDeviceAttributeMultiprocessorCount = 16 };
+// (memory pools: acf_api.hip's capture side asks for one and, here, is told that the runtime has none)
+typedef struct MockMemPool *hipMemPool_t;
+enum { hipMemAllocationTypePinned = 1, hipMemLocationTypeDevice = 1, hipMemPoolAttrReleaseThreshold = 4 };
+struct hipMemPoolProps { int allocType; struct { int type, id; } location; };
 struct dim3 { unsigned x, y, z; dim3(unsigned a = 1, unsigned b = 1, unsigned c = 1) : x(a), y(b), z(c) {} };
 
 extern "C" {
@@ -33,6 +37,10 @@ hipError_t hipMalloc(void **p, size_t n);
 hipError_t hipFree(void *p);
 hipError_t hipMallocAsync(void **p, size_t n, hipStream_t s);
 hipError_t hipFreeAsync(void *p, hipStream_t s);
+hipError_t hipMemPoolCreate(hipMemPool_t *pool, const hipMemPoolProps *props);
+hipError_t hipMemPoolSetAttribute(hipMemPool_t pool, int attr, void *value);
+hipError_t hipMemPoolDestroy(hipMemPool_t pool);
+hipError_t hipMallocFromPoolAsync(void **p, size_t n, hipMemPool_t pool, hipStream_t s);
 hipError_t hipHostMalloc(void **p, size_t n, unsigned flags);
 hipError_t hipHostFree(void *p);
 hipError_t hipMemcpy(void *dst, const void *src, size_t n, hipMemcpyKind k);

@@ -210,6 +210,10 @@ hipError_t hipFreeAsync(void *p, hipStream_t s) {
     if (it != g_buffers.end()) { munmap(it->second.base, it->second.maplen); g_buffers.erase(it); }
     return hipSuccess;
 }
+hipError_t hipMemPoolCreate(hipMemPool_t *, const hipMemPoolProps *) { return hipErrorInvalidValue; }      // (a runtime without pools)
+hipError_t hipMemPoolSetAttribute(hipMemPool_t, int, void *) { return hipErrorInvalidValue; }
+hipError_t hipMemPoolDestroy(hipMemPool_t) { return hipErrorInvalidValue; }
+hipError_t hipMallocFromPoolAsync(void **p, size_t n, hipMemPool_t, hipStream_t s) { return hipMallocAsync(p, n, s); }
 hipError_t hipHostMalloc(void **p, size_t n, unsigned) { *p = std::calloc(1, n ? n : 1); return *p ? hipSuccess : hipErrorInvalidValue; }
 hipError_t hipHostFree(void *p) { std::free(p); return hipSuccess; }
 
