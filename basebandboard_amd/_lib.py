@@ -6,6 +6,8 @@ there is no Python/NumPy/CPU fallback for any of the compute entry points.
 import ctypes as C
 import pathlib
 
+import torch
+
 _HERE = pathlib.Path(__file__).resolve().parent
 LIB_PATH = _HERE / "libbbb_hip.so"
 
@@ -294,6 +296,15 @@ def check(rc, what):
     raise BbbError(rc, f"{what} failed ({name})", detail)
 
 
+def cuda_tensor(name, t, dtypes, kind, device):
+    """t when it is a contiguous 1-D CUDA tensor of one of `dtypes` (named `kind` in the ValueError) on cuda:device."""
+    if not isinstance(t, torch.Tensor) or t.dtype not in dtypes or not t.is_cuda or t.dim() != 1 or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous 1-D {kind} CUDA tensor")
+    if t.device != torch.device("cuda", device):
+        raise ValueError(f"{name} must be on cuda:{device}")
+    return t
+
+
 class Handle:
     """Base of a class that owns an object of the C ABI: attribute `_handle` holds the raw pointer, the C function `_close`
     releases it.  close() (once; later calls do nothing), context manager, and a last close when collected."""
@@ -316,3 +327,20 @@ class Handle:
             self.close()
         except Exception:
             pass
+
+
+class StreamHandle(Handle):
+    """A Handle whose object (on `self.device`) runs on one stream at a time: opened on the current torch stream
+    (`_open_stream()`, the argument for the C open), moved by the C function `_set_stream` when a later call finds another
+    stream current (`_bind_stream()`, in front of every call that queues work)."""
+    _set_stream = None
+
+    def _open_stream(self):
+        self._stream = torch.cuda.current_stream(self.device).cuda_stream if torch.cuda.is_available() else None
+        return C.c_void_p(self._stream)
+
+    def _bind_stream(self):
+        s = torch.cuda.current_stream(self.device).cuda_stream
+        if s != self._stream:
+            check(getattr(lib(), self._set_stream)(getattr(self, self._handle), C.c_void_p(s)), self._set_stream)
+            self._stream = s

@@ -1,5 +1,6 @@
 // acf_api.hip -- the extern "C" entry points of the autocorrelation counters (include/bbb.h).  Host logic only: argument
 // checks and, on the transmitter side, what a chunk of tx_chunks.hpp's loop does and its scratch.
+#include "capture.hpp"
 #include "tx_chunks.hpp"
 
 #include <memory>
@@ -75,14 +76,9 @@ int bbb_acf_accumulate_i16(const int16_t *samples_dev, uint64_t nfirst, uint64_t
     const AcfPlan p = acf_plan(nlags, nfirst);
     if (p.gx < 0) return fail(BBB_EHIP, "could not size the correlator's grid");
     // the slab belongs to this call (stream-ordered allocation, as bbb_eye_accumulate_i16's)
-    uint64_t *scratch = nullptr;
-    if (hipMemPool_t pool = scratch_pool(device))
-        BBB_HIP(hipMallocFromPoolAsync((void **)&scratch, p.scratch_words * sizeof(uint64_t), pool, st));
-    else
-        BBB_HIP(hipMallocAsync((void **)&scratch, p.scratch_words * sizeof(uint64_t), st));
-    rc = acf_launch(p, samples_dev, nfirst, navail, nlags, scratch, reinterpret_cast<uint64_t *>(acf_dev), st);
-    (void)hipFreeAsync(scratch, st);
-    return rc;
+    CallScratch<uint64_t> scratch;
+    if ((rc = scratch.alloc(p.scratch_words, st, scratch_pool(device)))) return rc;
+    return acf_launch(p, samples_dev, nfirst, navail, nlags, scratch, reinterpret_cast<uint64_t *>(acf_dev), st);
 }
 
 int bbb_tx_acf_open(bbb_lutopt *h, const bbb_tx_cfg *cfg, uint32_t nlags, uint64_t chunk_samples, bbb_tx_acf **out) {

@@ -2,6 +2,7 @@
 // Host logic only: argument checks, GF(2) jump-ahead plans, workspace, kernel launches.
 #include "bbb_common.hpp"
 #include "dev_buf.hpp"
+#include "capture.hpp"
 #include "awgn_launch.hpp"
 #include "stage_common.hpp"
 #include "gf2.hpp"
@@ -1458,17 +1459,13 @@ int bbb_prbs_check(int k, uint64_t init_state, uint64_t first_bit, uint64_t nbit
     hipStream_t st = (hipStream_t)hip_stream;
     // the counter belongs to this call (stream-ordered allocation from the device's pool: microseconds, and
     // two threads or streams checking on one device never share it)
-    uint64_t *d = nullptr;
-    BBB_HIP(hipMallocAsync((void **)&d, sizeof(uint64_t), st));
-    hipError_t e = hipMemsetAsync(d, 0, sizeof(uint64_t), st);
-    rc = e == hipSuccess ? bbb_prbs_check_dev(k, init_state, first_bit, nbits, src_packed_dev, d, device, hip_stream)
-                         : fail(BBB_EHIP, std::string("hipMemsetAsync: ") + hipGetErrorString(e));
-    if (rc == BBB_OK) {
-        e = hipMemcpyAsync(nerr, d, sizeof(uint64_t), hipMemcpyDeviceToHost, st);
-        if (e != hipSuccess) rc = fail(BBB_EHIP, std::string("hipMemcpyAsync: ") + hipGetErrorString(e));
-    }
-    (void)hipFreeAsync(d, st);
-    if (rc) return rc;
+    {
+        CallScratch<uint64_t> d;
+        if ((rc = d.alloc(1, st))) return rc;
+        BBB_HIP(hipMemsetAsync(d, 0, sizeof(uint64_t), st));
+        if ((rc = bbb_prbs_check_dev(k, init_state, first_bit, nbits, src_packed_dev, d, device, hip_stream))) return rc;
+        BBB_HIP(hipMemcpyAsync(nerr, d, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    }                                                 // (released in front of the wait)
     BBB_HIP(hipStreamSynchronize(st));
     return BBB_OK;
 }
@@ -1531,14 +1528,12 @@ int bbb_shaper_fill_i16(const bbb_tx_cfg *cfg, int16_t *out_dev, uint64_t nsampl
     int64_t m0;
     uint64_t nbits;
     tx_bit_range(first_sample, nsamples, &m0, &nbits);
-    uint64_t *d_bits = nullptr;
+    CallScratch<uint64_t> d_bits;
     if (cfg->source == 0 && nbits) {
-        BBB_HIP(hipMallocAsync((void **)&d_bits, ((nbits + 63) / 64 + 2) * sizeof(uint64_t), st));
-        rc = prbs_fill_launch(cfg->prbs_k, cfg->prbs_state, (uint64_t)m0, nbits, d_bits, st);
+        if ((rc = d_bits.alloc((nbits + 63) / 64 + 2, st))) return rc;
+        if ((rc = prbs_fill_launch(cfg->prbs_k, cfg->prbs_state, (uint64_t)m0, nbits, d_bits, st))) return rc;
     }
-    if (!rc) rc = tx_waveform_launch(cfg->coeffs, d_bits, m0, d_bits ? nbits : 0, cfg->source, nullptr, 0, 1, 0, first_sample, nsamples, out_dev, st);
-    if (d_bits) (void)hipFreeAsync(d_bits, st);
-    return rc;
+    return tx_waveform_launch(cfg->coeffs, d_bits, m0, d_bits ? nbits : 0, cfg->source, nullptr, 0, 1, 0, first_sample, nsamples, out_dev, st);
 }
 
 int bbb_tx_fill_i16(bbb_lutopt *h, const bbb_tx_cfg *cfg, int16_t *out_dev, uint64_t nsamples, uint64_t first_sample) {

@@ -1,23 +1,12 @@
 // ddc_api.hip -- the extern "C" entry points of the digital down-converter (include/bbb.h, bbb_ddc_*).  Host logic only: the
 // argument checks, the launch structure (taps packed by fir_api.hip's rule, the oscillator's ROM) and the host CORDIC.
-#include "bbb_common.hpp"
+#include "capture.hpp"
 #include "ddc_common.hpp"
 
 #include <algorithm>
 #include <string>
 
 using namespace bbb;
-
-namespace {
-
-constexpr uint64_t kDdcSampleLimit = 1ull << 58;
-
-bool overlap(const void *a, uint64_t abytes, const void *b, uint64_t bbytes) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a0 < b0 + bbytes && b0 < a0 + abytes;
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -40,19 +29,18 @@ int bbb_ddc_run(const int16_t *in_dev, uint64_t nin, uint32_t nbefore, uint64_t 
     int rc = fir_cfg_check(fir, true);                  // out_bytes is not looked at; the shift is, here
     if (rc) return rc;
     if (fir->shift > 31) return fail(BBB_EINVAL, "shift must be 0..31 (got " + std::to_string(fir->shift) + ")");
-    if (first_sample > kDdcSampleLimit || nin > kDdcSampleLimit - first_sample) return fail(BBB_EINVAL, "first_sample + nin must be <= 2^58");
+    if (first_sample > kFirSampleLimit || nin > kFirSampleLimit - first_sample) return fail(BBB_EINVAL, "first_sample + nin must be <= 2^58");
     if (nin && !in_dev) return fail(BBB_EINVAL, "null in_dev");
-    const uint64_t nout = fir->phase < nin ? (nin - fir->phase + fir->decim - 1) / fir->decim : 0;
+    const uint64_t nout = fir_nout(fir, nin);
     if (nout && !out_dev) return fail(BBB_EINVAL, "null out_dev");
     const unsigned pair = ddc->mode == BBB_DDC_IQ32 ? 8 : 4;           // bytes of one output element
     if (((uintptr_t)in_dev & 1) || ((uintptr_t)out_dev & (pair - 1))) return fail(BBB_EINVAL, "misaligned device pointer");
-    const uint32_t before = std::min<uint32_t>(nbefore, fir->ntaps - 1);
-    if (nout && overlap(in_dev - before, (nin + before) * 2, out_dev, nout * pair)) return fail(BBB_EINVAL, "out_dev overlaps the samples");
+    uint32_t before;
+    if ((rc = fir_history(in_dev, nin, nbefore, fir->ntaps, out_dev, nout * pair, "out_dev", &before))) return rc;
     if (nout_out) *nout_out = nout;
     if (nout == 0) return BBB_OK;
-    if ((rc = use_device(device))) return rc;
     int cus = 0;
-    BBB_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
+    if ((rc = use_device(device)) || (rc = device_cus(device, &cus))) return rc;
     DdcLaunch a{};
     a.in = in_dev;
     a.out = out_dev;

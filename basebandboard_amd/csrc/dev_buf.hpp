@@ -1,5 +1,6 @@
 // dev_buf.hpp -- the owning device buffer of the host files (bbb_api.hip's scheduler, the transmitter-driven analysers of
-// tx_chunks.hpp).  Host only: no kernel file includes it.
+// tx_chunks.hpp, and through capture.hpp the capture side's objects: bbb_errstat, bbb_nco, bbb_sinc_eye).  Host only: no
+// kernel file includes it.
 #pragma once
 #include "bbb_common.hpp"
 

@@ -1,7 +1,7 @@
 // errstat_api.hip -- the extern "C" entry points of the error statistics (include/bbb.h, bbb_errstat_*).  Host logic only:
 // argument checks, the object's device memory (the result, which holds every counter and the carried state, and the tile
 // summaries of one launch) and the loop over launches.
-#include "bbb_common.hpp"
+#include "capture.hpp"
 
 #include <algorithm>
 #include <memory>
@@ -24,18 +24,11 @@ int cfg_check(const bbb_errstat_cfg *c) {
 }  // namespace
 
 struct bbb_errstat {
-    int device = -1;
-    hipStream_t st = nullptr;
     bbb_errstat_cfg cfg{};
     bool ended = false;                   // a call with nbits % 64 != 0 was queued: the record is over until reset
-    bbb_errstat_result *res = nullptr;    // device
-    void *scratch = nullptr;              // device: errstat_scratch_bytes()
-
-    ~bbb_errstat() {
-        if (device >= 0) (void)hipSetDevice(device);
-        if (res) (void)hipFree(res);
-        if (scratch) (void)hipFree(scratch);
-    }
+    DevBuf<unsigned char> scratch;        // the tile summaries of one launch: errstat_scratch_bytes()
+    DevBuf<bbb_errstat_result> res;       // every counter and the carried state
+    StreamObj on;                         // last: selects the device for the frees (res, then scratch)
 };
 
 extern "C" {
@@ -53,12 +46,11 @@ int bbb_errstat_open(const bbb_errstat_cfg *cfg, int device, void *hip_stream, b
     if (rc) return rc;
     if ((rc = use_device(device))) return rc;
     auto e = std::make_unique<bbb_errstat>();
-    e->device = device;
-    e->st = (hipStream_t)hip_stream;
+    e->on.device = device;
+    e->on.st = (hipStream_t)hip_stream;
     e->cfg = *cfg;
-    BBB_HIP(hipMalloc((void **)&e->res, sizeof(bbb_errstat_result)));
-    BBB_HIP(hipMalloc(&e->scratch, errstat_scratch_bytes()));
-    BBB_HIP(hipMemsetAsync(e->res, 0, sizeof(bbb_errstat_result), e->st));
+    if ((rc = e->res.grow(1)) || (rc = e->scratch.grow(errstat_scratch_bytes()))) return rc;
+    BBB_HIP(hipMemsetAsync(e->res, 0, sizeof(bbb_errstat_result), e->on.st));
     *out = e.release();
     return BBB_OK;
 }
@@ -69,7 +61,7 @@ int bbb_errstat_accumulate(bbb_errstat *e, const uint64_t *err_packed_dev, const
     if (nbits == 0) return BBB_OK;
     if (!err_packed_dev) return fail(BBB_EINVAL, "null err_packed_dev");
     if (((uintptr_t)err_packed_dev & 7) || ((uintptr_t)mask_packed_dev & 7)) return fail(BBB_EINVAL, "misaligned device pointer");
-    BBB_HIP(hipSetDevice(e->device));
+    BBB_HIP(hipSetDevice(e->on.device));
     ErrLaunch a{};
     a.guard = e->cfg.guard;
     a.nblock = e->cfg.nblock;
@@ -79,7 +71,7 @@ int bbb_errstat_accumulate(bbb_errstat *e, const uint64_t *err_packed_dev, const
         a.nbits = std::min(kErrLaunchBits, nbits - off);
         a.err = err_packed_dev + off / 64;
         a.mask = mask_packed_dev ? mask_packed_dev + off / 64 : nullptr;
-        int rc = errstat_launch(a, e->res, e->scratch, e->st);
+        int rc = errstat_launch(a, e->res, e->scratch, e->on.st);
         if (rc) return rc;
     }
     if (nbits & 63) e->ended = true;
@@ -90,8 +82,8 @@ int bbb_errstat_skip(bbb_errstat *e, uint64_t nbits) {
     if (!e) return fail(BBB_EINVAL, "null errstat object");
     if (e->ended) return fail(BBB_EINVAL, "the record ended with a call whose nbits was no multiple of 64: reset first");
     if (nbits == 0) return BBB_OK;
-    BBB_HIP(hipSetDevice(e->device));
-    int rc = errstat_skip_launch(e->res, nbits, e->st);
+    BBB_HIP(hipSetDevice(e->on.device));
+    int rc = errstat_skip_launch(e->res, nbits, e->on.st);
     if (rc) return rc;
     if (nbits & 63) e->ended = true;
     return BBB_OK;
@@ -100,41 +92,30 @@ int bbb_errstat_skip(bbb_errstat *e, uint64_t nbits) {
 int bbb_errstat_read(bbb_errstat *e, bbb_errstat_result *out) {
     if (!e) return fail(BBB_EINVAL, "null errstat object");
     if (!out) return fail(BBB_EINVAL, "null result");
-    BBB_HIP(hipSetDevice(e->device));
+    BBB_HIP(hipSetDevice(e->on.device));
     auto r = std::make_unique<bbb_errstat_result>();
-    BBB_HIP(hipMemcpyAsync(r.get(), e->res, sizeof *r, hipMemcpyDeviceToHost, e->st));
-    BBB_HIP(hipStreamSynchronize(e->st));
+    BBB_HIP(hipMemcpyAsync(r.get(), e->res, sizeof *r, hipMemcpyDeviceToHost, e->on.st));
+    BBB_HIP(hipStreamSynchronize(e->on.st));
     *out = *r;
     return BBB_OK;
 }
 
 int bbb_errstat_reset(bbb_errstat *e) {
     if (!e) return fail(BBB_EINVAL, "null errstat object");
-    BBB_HIP(hipSetDevice(e->device));
-    BBB_HIP(hipMemsetAsync(e->res, 0, sizeof(bbb_errstat_result), e->st));
+    BBB_HIP(hipSetDevice(e->on.device));
+    BBB_HIP(hipMemsetAsync(e->res, 0, sizeof(bbb_errstat_result), e->on.st));
     e->ended = false;
     return BBB_OK;
 }
 
 int bbb_errstat_set_stream(bbb_errstat *e, void *hip_stream) {
     if (!e) return fail(BBB_EINVAL, "null errstat object");
-    hipStream_t s = (hipStream_t)hip_stream;
-    if (s == e->st) return BBB_OK;
-    BBB_HIP(hipSetDevice(e->device));
-    hipEvent_t ev;
-    BBB_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    hipError_t err = hipEventRecord(ev, e->st);
-    if (err == hipSuccess) err = hipStreamWaitEvent(s, ev, 0);
-    (void)hipEventDestroy(ev);
-    if (err != hipSuccess) return fail(BBB_EHIP, std::string("ordering the new stream: ") + hipGetErrorString(err));
-    e->st = s;
-    return BBB_OK;
+    return e->on.rebind((hipStream_t)hip_stream);
 }
 
 int bbb_errstat_close(bbb_errstat *e) {
     if (!e) return fail(BBB_EINVAL, "null errstat object");
-    if (e->device >= 0) (void)hipSetDevice(e->device);
-    (void)hipStreamSynchronize(e->st);    // the object's buffers may still be in use by queued launches
+    e->on.drain();
     delete e;
     return BBB_OK;
 }

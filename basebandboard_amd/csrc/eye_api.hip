@@ -1,5 +1,6 @@
 // eye_api.hip -- the extern "C" entry points of the eye diagram and bathtub (include/bbb.h).  Host logic only: argument
 // checks and, on the transmitter side, what a chunk of tx_chunks.hpp's loop does and its scratch.
+#include "capture.hpp"
 #include "tx_chunks.hpp"
 
 #include <memory>
@@ -57,13 +58,11 @@ int bbb_eye_accumulate_i16(const int16_t *samples_dev, uint64_t nsamples, uint64
     const int blocks = eye_grid_blocks(nsamples);
     if (blocks < 0) return blocks;
     // the slab belongs to this call (stream-ordered allocation from the device's pool, as bbb_prbs_check's counter)
-    uint32_t *scratch = nullptr;
-    BBB_HIP(hipMallocAsync((void **)&scratch, eye_scratch_words(blocks, eye->ncols) * sizeof(uint32_t), st));
+    CallScratch<uint32_t> scratch;
+    if ((rc = scratch.alloc(eye_scratch_words(blocks, eye->ncols), st))) return rc;
     EyeLaunch a = launch_of(*eye);
     a.want_hist = 1;
-    rc = eye_accumulate_launch(a, samples_dev, nsamples, first_sample, scratch, blocks, hist_dev, nullptr, st);
-    (void)hipFreeAsync(scratch, st);
-    return rc;
+    return eye_accumulate_launch(a, samples_dev, nsamples, first_sample, scratch, blocks, hist_dev, nullptr, st);
 }
 
 int bbb_tx_eye_open(bbb_lutopt *h, const bbb_tx_cfg *cfg, const bbb_eye_cfg *eye, uint64_t chunk_samples, bbb_tx_eye **out) {

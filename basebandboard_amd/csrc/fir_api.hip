@@ -1,6 +1,6 @@
 // fir_api.hip -- the extern "C" entry points of the FIR filter (include/bbb.h, bbb_fir_*).  Host logic only: the checks of
 // bbb_fir_cfg, the packing of the taps into the launch structure, and the moving-average presets.
-#include "bbb_common.hpp"
+#include "capture.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -10,31 +10,22 @@ using namespace bbb;
 
 namespace {
 
-constexpr uint64_t kFirSampleLimit = 1ull << 58;
-
-bool overlap(const void *a, uint64_t abytes, const void *b, uint64_t bbytes) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a0 < b0 + bbytes && b0 < a0 + abytes;
-}
-
 // mode 0 / 1: out_dev holds int16 / int32 samples; 2: packed decisions
 int run(const int16_t *in_dev, uint64_t nin, uint32_t nbefore, const bbb_fir_cfg *cfg, int mode, int32_t threshold, int strict,
         void *out_dev, uint64_t *nout_out, int device, hipStream_t st) {
     if (nin > kFirSampleLimit) return fail(BBB_EINVAL, "nin must be <= 2^58");
     if (nin && !in_dev) return fail(BBB_EINVAL, "null in_dev");
-    const uint64_t nout = cfg->phase < nin ? (nin - cfg->phase + cfg->decim - 1) / cfg->decim : 0;
+    const uint64_t nout = fir_nout(cfg, nin);
     if (nout && !out_dev) return fail(BBB_EINVAL, mode == 2 ? "null bits_packed_dev" : "null out_dev");
     const uint64_t obytes = mode == 2 ? (nout + 63) / 64 * 8 : nout * (mode ? 4 : 2);
     if (((uintptr_t)in_dev & 1) || ((uintptr_t)out_dev & (mode == 2 ? 7 : mode ? 3 : 1))) return fail(BBB_EINVAL, "misaligned device pointer");
-    const uint32_t before = std::min<uint32_t>(nbefore, cfg->ntaps - 1);
-    if (nout && overlap(in_dev - before, (nin + before) * 2, out_dev, obytes))
-        return fail(BBB_EINVAL, mode == 2 ? "bits_packed_dev overlaps the samples" : "out_dev overlaps the samples");
+    uint32_t before;
+    int rc = fir_history(in_dev, nin, nbefore, cfg->ntaps, out_dev, obytes, mode == 2 ? "bits_packed_dev" : "out_dev", &before);
+    if (rc) return rc;
     if (nout_out) *nout_out = nout;
     if (nout == 0) return BBB_OK;
-    int rc = use_device(device);
-    if (rc) return rc;
     int cus = 0;
-    BBB_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
+    if ((rc = use_device(device)) || (rc = device_cus(device, &cus))) return rc;
     FirLaunch a{};
     a.in = in_dev;
     a.out = out_dev;

@@ -6,7 +6,7 @@
 // mover's place.
 // What a call owns (its partial histograms, and the chunk buffer of the generators that have no planes form) is allocated
 // stream-ordered from the device's pool on the handle's stream and released behind the last kernel, as bbb_eye_accumulate_i16's slab.
-#include "bbb_common.hpp"
+#include "capture.hpp"
 
 #include <algorithm>
 #include <string>
@@ -97,16 +97,12 @@ int bbb_awgn_hist(bbb_lutopt *h, uint64_t *hist_dev, uint64_t nsamples, uint64_t
         if (!(fused_ok && n >= kHistFusedMin)) buffered = std::max(buffered, n);
         off += n;
     }
-    void *buf = nullptr;
-    BBB_HIP(hipMallocAsync((void **)&c.scratch, (size_t)c.blocks * (size_t)k * sizeof(uint32_t), st));
-    if (buffered) {
-        // (a fill may write up to the next multiple of 16 samples)
-        const hipError_t e = hipMallocAsync(&buf, (size_t)((buffered + 15) & ~15ull) * (k > 256 ? 2 : 1) + 256, st);
-        if (e != hipSuccess) {
-            (void)hipFreeAsync(c.scratch, st);
-            return fail(BBB_EHIP, std::string("hipMallocAsync: ") + hipGetErrorString(e));
-        }
-    }
+    CallScratch<uint32_t> scratch;                    // released last: the chunk buffer, declared behind it, goes first
+    CallScratch<char> buf;
+    if ((rc = scratch.alloc((size_t)c.blocks * (size_t)k, st))) return rc;
+    c.scratch = scratch;
+    // (a fill may write up to the next multiple of 16 samples)
+    if (buffered && (rc = buf.alloc((size_t)((buffered + 15) & ~15ull) * (k > 256 ? 2 : 1) + 256, st))) return rc;
     // The planes form runs as the stream does at one read per sample kernel (level 1): the announcements of bbb_awgn_prefetch then
     // match the chunks.  The handle's own level comes back behind the call; what a look-ahead level had produced ahead is
     // dropped, as bbb_lutopt_set_staged says of every call of it.
@@ -118,9 +114,7 @@ int bbb_awgn_hist(bbb_lutopt *h, uint64_t *hist_dev, uint64_t nsamples, uint64_t
         const int rc2 = bbb_lutopt_set_staged(h, level);
         if (!rc) rc = rc2;
     }
-    (void)hipSetDevice(device);
-    if (buf) (void)hipFreeAsync(buf, st);
-    (void)hipFreeAsync(c.scratch, st);
+    (void)hipSetDevice(device);                       // for the two releases
     return rc;
 }
 

@@ -1,6 +1,6 @@
 // nco_api.hip -- the extern "C" entry points of the numerically controlled oscillator (include/bbb.h, bbb_nco_*).  Host logic
 // only: argument checks, the ROM, the object's device state (two slots, alternated by the launches) and the chunk loop.
-#include "bbb_common.hpp"
+#include "capture.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -33,21 +33,13 @@ int state_check(const bbb_nco_state *s) {
 }  // namespace
 
 struct bbb_nco {
-    int device = -1;
-    hipStream_t st = nullptr;
     bbb_nco_cfg cfg{};
     int grid = 0;
     int cur = 0;                     // the slot of state holding the registers after the last queued launch
-    int16_t *rom = nullptr;          // 1024 entries
-    bbb_nco_state *state = nullptr;  // 2 slots
-    uint32_t *tiles = nullptr;       // the fm scan's tile sums / offsets of one chunk
-
-    ~bbb_nco() {
-        if (device >= 0) (void)hipSetDevice(device);
-        if (rom) (void)hipFree(rom);
-        if (state) (void)hipFree(state);
-        if (tiles) (void)hipFree(tiles);
-    }
+    DevBuf<uint32_t> tiles;          // the fm scan's tile sums / offsets of one chunk
+    DevBuf<bbb_nco_state> state;     // 2 slots
+    DevBuf<int16_t> rom;             // 1024 entries
+    StreamObj on;                    // last: selects the device for the frees (rom, state, tiles)
 };
 
 extern "C" {
@@ -70,20 +62,18 @@ int bbb_nco_open(const bbb_nco_cfg *cfg, int device, void *hip_stream, bbb_nco *
     if (rc) return rc;
     if ((rc = use_device(device))) return rc;
     auto o = std::make_unique<bbb_nco>();
-    o->device = device;
-    o->st = (hipStream_t)hip_stream;
+    o->on.device = device;
+    o->on.st = (hipStream_t)hip_stream;
     o->cfg = *cfg;
     int cus = 0;
-    BBB_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
+    if ((rc = device_cus(device, &cus))) return rc;
     o->grid = std::max(1, cus) * 4;        // 4 workgroups of 512 threads fit a CU beside the 32 KiB of ROM replicas each
     int16_t rom[1024];
     bbb_nco_rom(rom);
-    BBB_HIP(hipMalloc((void **)&o->rom, sizeof rom));
-    BBB_HIP(hipMalloc((void **)&o->state, 2 * sizeof(bbb_nco_state)));
-    BBB_HIP(hipMalloc((void **)&o->tiles, nco_tiles(kChunkFm) * sizeof(uint32_t)));
-    BBB_HIP(hipMemcpyAsync(o->rom, rom, sizeof rom, hipMemcpyHostToDevice, o->st));
-    BBB_HIP(hipMemsetAsync(o->state, 0, 2 * sizeof(bbb_nco_state), o->st));
-    BBB_HIP(hipStreamSynchronize(o->st));  // `rom` is a host stack array
+    if ((rc = o->rom.grow(1024)) || (rc = o->state.grow(2)) || (rc = o->tiles.grow(nco_tiles(kChunkFm)))) return rc;
+    BBB_HIP(hipMemcpyAsync(o->rom, rom, sizeof rom, hipMemcpyHostToDevice, o->on.st));
+    BBB_HIP(hipMemsetAsync(o->state, 0, 2 * sizeof(bbb_nco_state), o->on.st));
+    BBB_HIP(hipStreamSynchronize(o->on.st));  // `rom` is a host stack array
     *out = o.release();
     return BBB_OK;
 }
@@ -98,17 +88,7 @@ int bbb_nco_set_cfg(bbb_nco *o, const bbb_nco_cfg *cfg) {
 
 int bbb_nco_set_stream(bbb_nco *o, void *hip_stream) {
     if (!o) return fail(BBB_EINVAL, "null nco object");
-    hipStream_t s = (hipStream_t)hip_stream;
-    if (s == o->st) return BBB_OK;
-    BBB_HIP(hipSetDevice(o->device));
-    hipEvent_t ev;
-    BBB_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    hipError_t e = hipEventRecord(ev, o->st);
-    if (e == hipSuccess) e = hipStreamWaitEvent(s, ev, 0);
-    (void)hipEventDestroy(ev);
-    if (e != hipSuccess) return fail(BBB_EHIP, std::string("ordering the new stream: ") + hipGetErrorString(e));
-    o->st = s;
-    return BBB_OK;
+    return o->on.rebind((hipStream_t)hip_stream);
 }
 
 int bbb_nco_run(bbb_nco *o, const int32_t *fm_dev, const uint16_t *am_dev, const int16_t *pm_dev, uint64_t nsamples,
@@ -118,7 +98,7 @@ int bbb_nco_run(bbb_nco *o, const int32_t *fm_dev, const uint16_t *am_dev, const
     if (!x_dev) return fail(BBB_EINVAL, "null x_dev");
     if (((uintptr_t)x_dev & 1) || ((uintptr_t)fm_dev & 3) || ((uintptr_t)am_dev & 1) || ((uintptr_t)pm_dev & 1))
         return fail(BBB_EINVAL, "misaligned device pointer");
-    BBB_HIP(hipSetDevice(o->device));
+    BBB_HIP(hipSetDevice(o->on.device));
     NcoLaunch a{};
     a.fcw = o->cfg.fcw;
     a.am_c = o->cfg.am;
@@ -136,7 +116,7 @@ int bbb_nco_run(bbb_nco *o, const int32_t *fm_dev, const uint16_t *am_dev, const
         a.x = x_dev + off;
         a.in = o->state + o->cur;
         a.out = o->state + (o->cur ^ 1);
-        int rc = nco_launch(a, o->grid, o->st);
+        int rc = nco_launch(a, o->grid, o->on.st);
         if (rc) return rc;
         o->cur ^= 1;
     }
@@ -146,10 +126,10 @@ int bbb_nco_run(bbb_nco *o, const int32_t *fm_dev, const uint16_t *am_dev, const
 int bbb_nco_get_state(bbb_nco *o, bbb_nco_state *st) {
     if (!o) return fail(BBB_EINVAL, "null nco object");
     if (!st) return fail(BBB_EINVAL, "null state");
-    BBB_HIP(hipSetDevice(o->device));
+    BBB_HIP(hipSetDevice(o->on.device));
     bbb_nco_state s;
-    BBB_HIP(hipMemcpyAsync(&s, o->state + o->cur, sizeof s, hipMemcpyDeviceToHost, o->st));
-    BBB_HIP(hipStreamSynchronize(o->st));
+    BBB_HIP(hipMemcpyAsync(&s, o->state + o->cur, sizeof s, hipMemcpyDeviceToHost, o->on.st));
+    BBB_HIP(hipStreamSynchronize(o->on.st));
     *st = s;
     return BBB_OK;
 }
@@ -158,14 +138,13 @@ int bbb_nco_set_state(bbb_nco *o, const bbb_nco_state *st) {
     if (!o) return fail(BBB_EINVAL, "null nco object");
     int rc = state_check(st);
     if (rc) return rc;
-    BBB_HIP(hipSetDevice(o->device));
-    return nco_put_state(*st, o->state + o->cur, o->st);
+    BBB_HIP(hipSetDevice(o->on.device));
+    return nco_put_state(*st, o->state + o->cur, o->on.st);
 }
 
 int bbb_nco_close(bbb_nco *o) {
     if (!o) return fail(BBB_EINVAL, "null nco object");
-    if (o->device >= 0) (void)hipSetDevice(o->device);
-    (void)hipStreamSynchronize(o->st);     // the object's buffers may still be in use by queued launches
+    o->on.drain();
     delete o;
     return BBB_OK;
 }

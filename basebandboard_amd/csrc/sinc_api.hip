@@ -1,7 +1,7 @@
 // sinc_api.hip -- the extern "C" entry points of the 16x sinc interpolator (include/bbb.h, bbb_sinc_*).  Host logic only:
 // the coefficient table, argument checks, and the interpolated eye's chunk loop, which uses public calls only
 // (bbb_sinc_interpolate into the object's chunk, then bbb_eye_accumulate_i16).
-#include "bbb_common.hpp"
+#include "capture.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -57,14 +57,8 @@ struct bbb_sinc_eye {
     bbb_sinc_cfg cfg{};
     bbb_eye_cfg eye{};
     uint64_t chunk = 0;
-    int device = -1;
-    hipStream_t st = nullptr;
-    int16_t *buf = nullptr;          // the chunk's interpolated samples
-
-    ~bbb_sinc_eye() {
-        if (device >= 0) (void)hipSetDevice(device);
-        if (buf) (void)hipFree(buf);
-    }
+    DevBuf<int16_t> buf;             // the chunk's interpolated samples
+    StreamObj on;                    // last: selects the device for the free
 };
 
 extern "C" {
@@ -87,7 +81,7 @@ int bbb_sinc_interpolate(const void *in_dev, uint64_t nin, uint32_t nbefore, con
     if (nin == 0) return BBB_OK;
     if ((rc = use_device(device))) return rc;
     int cus = 0;
-    BBB_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
+    if ((rc = device_cus(device, &cus))) return rc;
     SincLaunch a{};
     a.in = in_dev;
     a.out = out_dev;
@@ -106,10 +100,7 @@ int bbb_sinc_eye_open(const bbb_sinc_cfg *cfg, const bbb_eye_cfg *eye, uint64_t 
     if (!out) return fail(BBB_EINVAL, "null out");
     int rc = cfg_check(cfg, true);
     if (rc) return rc;
-    if (!eye) return fail(BBB_EINVAL, "null eye cfg");
-    if (eye->ncols != 8 && eye->ncols != 16 && eye->ncols != 32 && eye->ncols != 64)
-        return fail(BBB_EINVAL, "eye ncols must be 8, 16, 32 or 64 (got " + std::to_string(eye->ncols) + ")");
-    if (eye->shift > 15) return fail(BBB_EINVAL, "eye shift must be 0..15 (got " + std::to_string(eye->shift) + ")");
+    if ((rc = eye_cfg_check(eye))) return rc;
     if (chunk_in > kSincChunkMax) return fail(BBB_EINVAL, "chunk_in must be <= 2^27");
     if ((rc = use_device(device))) return rc;
     auto e = std::make_unique<bbb_sinc_eye>();
@@ -117,9 +108,9 @@ int bbb_sinc_eye_open(const bbb_sinc_cfg *cfg, const bbb_eye_cfg *eye, uint64_t 
     e->cfg.out_bytes = 2;
     e->eye = *eye;
     e->chunk = chunk_in ? chunk_in : kSincChunkDefault;
-    e->device = device;
-    e->st = (hipStream_t)hip_stream;
-    BBB_HIP(hipMalloc((void **)&e->buf, e->chunk * BBB_SINC_UP * sizeof(int16_t)));
+    e->on.device = device;
+    e->on.st = (hipStream_t)hip_stream;
+    if ((rc = e->buf.grow(e->chunk * BBB_SINC_UP))) return rc;
     *out = e.release();
     return BBB_OK;
 }
@@ -136,10 +127,10 @@ int bbb_sinc_eye_run(bbb_sinc_eye *e, const void *in_dev, uint64_t nin, uint32_t
         const uint64_t n = std::min(e->chunk, nin - off);
         const uint32_t before = (uint32_t)std::min<uint64_t>(off + nbefore, BBB_SINC_TAPS - 1);
         int rc = bbb_sinc_interpolate(static_cast<const char *>(in_dev) + off * e->cfg.in_bytes, n, before, &e->cfg, e->buf,
-                                      e->device, e->st);
+                                      e->on.device, e->on.st);
         if (rc) return rc;
         if ((rc = bbb_eye_accumulate_i16(e->buf, n * BBB_SINC_UP, (first_sample + off) * BBB_SINC_UP, &e->eye, hist_dev,
-                                         e->device, e->st)))
+                                         e->on.device, e->on.st)))
             return rc;
         off += n;
     }
@@ -148,8 +139,7 @@ int bbb_sinc_eye_run(bbb_sinc_eye *e, const void *in_dev, uint64_t nin, uint32_t
 
 int bbb_sinc_eye_close(bbb_sinc_eye *e) {
     if (!e) return fail(BBB_EINVAL, "null sinc eye object");
-    if (e->device >= 0) (void)hipSetDevice(e->device);
-    (void)hipStreamSynchronize(e->st);     // the chunk may still be in use by queued launches
+    e->on.drain();
     delete e;
     return BBB_OK;
 }

@@ -1,5 +1,6 @@
 // xcorr_api.hip -- the extern "C" entry points of the data-to-waveform correlation (include/bbb.h).  Host logic only:
 // argument checks and, on the transmitter side, what a chunk of tx_chunks.hpp's loop does and its scratch.
+#include "capture.hpp"
 #include "tx_chunks.hpp"
 
 #include <memory>
@@ -62,12 +63,10 @@ int bbb_xcorr_accumulate_i16(const int16_t *samples_dev, uint64_t nsamples, uint
     const XcorrPlan p = xcorr_plan(cfg->spb, cfg->nlags, nsamples);
     if (p.gx < 0) return fail(BBB_EHIP, "could not size the correlator's grid");
     // the slab belongs to this call (stream-ordered allocation, as bbb_eye_accumulate_i16's)
-    uint64_t *scratch = nullptr;
-    BBB_HIP(hipMallocAsync((void **)&scratch, p.scratch_words * sizeof(uint64_t), st));
+    CallScratch<uint64_t> scratch;
+    if ((rc = scratch.alloc(p.scratch_words, st))) return rc;
     const XcorrLaunch l{samples_dev, nsamples, first_sample, bits_packed_dev, bit0, nbits, cfg->spb, cfg->nlags, cfg->origin};
-    rc = xcorr_launch(p, l, scratch, xc_dev, st);
-    (void)hipFreeAsync(scratch, st);
-    return rc;
+    return xcorr_launch(p, l, scratch, xc_dev, st);
 }
 
 int bbb_tx_xcorr_open(bbb_lutopt *h, const bbb_tx_cfg *cfg, uint32_t nlags, uint64_t chunk_samples, bbb_tx_xcorr **out) {

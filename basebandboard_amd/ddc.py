@@ -15,7 +15,7 @@ import ctypes as C
 import torch
 
 from . import _lib
-from .fir import FIR, nout as fir_nout, next_phase
+from .fir import FIR, Carry, nout as fir_nout, next_phase
 
 _MODE = {torch.int16: _lib.DDC_IQ16, torch.int32: _lib.DDC_IQ32}
 
@@ -100,10 +100,9 @@ def _polar_views(t):
     return t[:, 0].view(torch.uint16), t[:, 1]
 
 
-class DDCStream:
-    """A record converted piece by piece.  As FIRStream, the object keeps the last len(taps) - 1 samples in a buffer it
-    owns, in front of which every chunk is copied; it carries the decimation phase (fir.next_phase) and the running sample
-    number, which is all the oscillator needs."""
+class DDCStream(Carry):
+    """A record converted piece by piece.  As FIRStream, the object is the fir.Carry of the last len(taps) - 1 samples; it
+    carries the decimation phase (fir.next_phase) and the running sample number, which is all the oscillator needs."""
 
     def __init__(self, ddc, first_sample=0, out_dtype=torch.int16, polar=False):
         if out_dtype not in _MODE:
@@ -111,28 +110,15 @@ class DDCStream:
         self.ddc, self.polar = ddc, bool(polar)
         self.mode = _lib.DDC_POLAR if polar else _MODE[out_dtype]
         self.phase, self.first_sample = ddc.phase, int(first_sample)
-        self.keep = len(ddc.fir.taps) - 1
-        self.lead = (self.keep + 7) // 8 * 8          # the chunk starts at this element of the buffer
-        self.have = 0                                 # history samples held, at buf[lead - have : lead]
-        self.buf = None
+        super().__init__(len(ddc.fir.taps) - 1)
 
     def push(self, chunk):
         """[nout, 2] of the chunk ((mag, phase) views with polar=True)."""
         self.ddc.fir._samples(chunk, 0)
         n = chunk.numel()
-        if self.buf is None or self.buf.numel() < self.lead + n:
-            new = torch.empty(self.lead + max(n, 1), dtype=torch.int16, device=chunk.device)
-            if self.have:
-                new[self.lead - self.have:self.lead] = self.buf[self.lead - self.have:self.lead]
-            self.buf = new
-        self.buf[self.lead:self.lead + n] = chunk
-        out = self.ddc._run(self.buf[self.lead - self.have:self.lead + n], self.first_sample, self.have, self.mode, None,
-                            phase=self.phase)
-        have = min(self.keep, self.have + n)
-        if have:
-            # the tail of [history | chunk] becomes the history; the clone keeps an overlapping move exact
-            self.buf[self.lead - have:self.lead] = self.buf[self.lead + n - have:self.lead + n].clone()
-        self.have = have
+        samples, nbefore = self.place(chunk)
+        out = self.ddc._run(samples, self.first_sample, nbefore, self.mode, None, phase=self.phase)
+        self.advance(n)
         self.phase = next_phase(self.phase, self.ddc.decim, n)
         self.first_sample += n
         return _polar_views(out) if self.polar else out

@@ -74,7 +74,9 @@ def summarise(res, block_bits=(), close=True):
     return out
 
 
-class ErrorStats:
+class ErrorStats(_lib.StreamHandle):
+    _handle, _close, _set_stream = "_o", "bbb_errstat_close", "bbb_errstat_set_stream"
+
     def __init__(self, guard=0, block_bits=(), device=0):
         block_bits = [int(b) for b in block_bits]
         if not 0 <= int(guard) < 1 << 32:
@@ -85,17 +87,9 @@ class ErrorStats:
             raise ValueError("block_bits must be in [1, 2^40)")
         self.guard, self.block_bits, self.device = int(guard), block_bits, int(device)
         cfg = _lib.ErrstatCfg(self.guard, len(block_bits), (C.c_uint64 * 4)(*block_bits))
-        self._stream = torch.cuda.current_stream(self.device).cuda_stream if torch.cuda.is_available() else None
         o = C.c_void_p()
-        _lib.check(_lib.lib().bbb_errstat_open(C.byref(cfg), self.device, C.c_void_p(self._stream), C.byref(o)),
-                   "bbb_errstat_open")
+        _lib.check(_lib.lib().bbb_errstat_open(C.byref(cfg), self.device, self._open_stream(), C.byref(o)), "bbb_errstat_open")
         self._o = o
-
-    def _bind_stream(self):
-        s = torch.cuda.current_stream(self.device).cuda_stream
-        if s != self._stream:
-            _lib.check(_lib.lib().bbb_errstat_set_stream(self._o, C.c_void_p(s)), "bbb_errstat_set_stream")
-            self._stream = s
 
     def _packed(self, name, t):
         if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or not t.is_cuda or not t.is_contiguous():
@@ -145,20 +139,3 @@ class ErrorStats:
         """Everything counted so far (`summarise`); waits for the calls queued so far.  The device state is untouched: more
         data may follow, and a later result closes whatever burst is open then."""
         return summarise(self.read(), self.block_bits, close)
-
-    def close(self):
-        o, self._o = getattr(self, "_o", None), None
-        if o:
-            _lib.check(_lib.lib().bbb_errstat_close(o), "bbb_errstat_close")
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

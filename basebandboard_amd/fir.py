@@ -95,11 +95,7 @@ class FIR:
         return c
 
     def _samples(self, samples, nbefore):
-        if (not isinstance(samples, torch.Tensor) or samples.dtype != torch.int16 or not samples.is_cuda or samples.dim() != 1
-                or not samples.is_contiguous()):
-            raise ValueError("samples must be a contiguous 1-D int16 CUDA tensor")
-        if (samples.device.index or 0) != self.device:
-            raise ValueError(f"samples must be on cuda:{self.device}")
+        _lib.cuda_tensor("samples", samples, (torch.int16,), "int16", self.device)
         nbefore = int(nbefore)
         if not 0 <= nbefore <= samples.numel():
             raise ValueError("nbefore must be 0 .. len(samples)")
@@ -151,23 +147,19 @@ class FIR:
         return FIRStream(self, decim, phase, out_dtype)
 
 
-class FIRStream:
-    """A record filtered piece by piece.  The object keeps the last len(taps) - 1 samples in a buffer it owns, in front of
-    which every chunk is copied (so that the filter reads the chunk from a 16-byte aligned address), and carries the
-    phase: after a chunk of n samples it is (phase - n) mod decim."""
+class Carry:
+    """The history of a record handed over in pieces (FIRStream, ddc.DDCStream): the last `keep` samples, in a buffer the
+    object owns, in front of which every chunk is copied (so that the filter reads the chunk from a 16-byte aligned
+    address)."""
 
-    def __init__(self, fir, decim=1, phase=0, out_dtype=torch.int16):
-        fir._cfg(decim, phase)
-        if out_dtype not in _DT:
-            raise ValueError("out_dtype must be torch.int16 or torch.int32")
-        self.fir, self.decim, self.phase, self.out_dtype = fir, int(decim), int(phase), out_dtype
-        self.keep = len(fir.taps) - 1
-        self.lead = (self.keep + 7) // 8 * 8          # the chunk starts at this element of the buffer
+    def __init__(self, keep):
+        self.keep = keep
+        self.lead = (keep + 7) // 8 * 8               # the chunk starts at this element of the buffer
         self.have = 0                                 # history samples held, at buf[lead - have : lead]
         self.buf = None
 
-    def push(self, chunk):
-        self.fir._samples(chunk, 0)
+    def place(self, chunk):
+        """Copies the chunk behind the history: ([history | chunk], nbefore) to hand to the filter."""
         n = chunk.numel()
         if self.buf is None or self.buf.numel() < self.lead + n:
             new = torch.empty(self.lead + max(n, 1), dtype=torch.int16, device=chunk.device)
@@ -175,12 +167,32 @@ class FIRStream:
                 new[self.lead - self.have:self.lead] = self.buf[self.lead - self.have:self.lead]
             self.buf = new
         self.buf[self.lead:self.lead + n] = chunk
-        out = self.fir.filter(self.buf[self.lead - self.have:self.lead + n], self.decim, self.phase, nbefore=self.have,
-                              out_dtype=self.out_dtype)
+        return self.buf[self.lead - self.have:self.lead + n], self.have
+
+    def advance(self, n):
+        """Behind the filter's call: the tail of [history | chunk of n] becomes the history."""
         have = min(self.keep, self.have + n)
         if have:
-            # the tail of [history | chunk] becomes the history; the clone keeps an overlapping move exact
+            # (the clone keeps an overlapping move exact)
             self.buf[self.lead - have:self.lead] = self.buf[self.lead + n - have:self.lead + n].clone()
         self.have = have
-        self.phase = next_phase(self.phase, self.decim, n)
+
+
+class FIRStream(Carry):
+    """A record filtered piece by piece: the Carry of the last len(taps) - 1 samples, and the phase, which after a chunk of
+    n samples is (phase - n) mod decim."""
+
+    def __init__(self, fir, decim=1, phase=0, out_dtype=torch.int16):
+        fir._cfg(decim, phase)
+        if out_dtype not in _DT:
+            raise ValueError("out_dtype must be torch.int16 or torch.int32")
+        self.fir, self.decim, self.phase, self.out_dtype = fir, int(decim), int(phase), out_dtype
+        super().__init__(len(fir.taps) - 1)
+
+    def push(self, chunk):
+        self.fir._samples(chunk, 0)
+        samples, nbefore = self.place(chunk)
+        out = self.fir.filter(samples, self.decim, self.phase, nbefore=nbefore, out_dtype=self.out_dtype)
+        self.advance(chunk.numel())
+        self.phase = next_phase(self.phase, self.decim, chunk.numel())
         return out

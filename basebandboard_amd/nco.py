@@ -27,16 +27,16 @@ def _int_in(name, v, lo, hi):
     return int(v)
 
 
-class NCO:
+class NCO(_lib.StreamHandle):
+    _handle, _close, _set_stream = "_o", "bbb_nco_close", "bbb_nco_set_stream"
+
     def __init__(self, fcw, am=0xFFFF, fm=0, pm=0, n=24, m=10, p=16, device=0):
         if (n, m, p) != (24, 10, 16):
             raise ValueError("only the reference's widths n=24, m=10, p=16 are implemented")
         self.device = int(device)
         self._cfg = self._make_cfg(fcw, am, fm, pm)
-        self._stream = torch.cuda.current_stream(self.device).cuda_stream if torch.cuda.is_available() else None
         o = C.c_void_p()
-        _lib.check(_lib.lib().bbb_nco_open(C.byref(self._cfg), self.device, C.c_void_p(self._stream), C.byref(o)),
-                   "bbb_nco_open")
+        _lib.check(_lib.lib().bbb_nco_open(C.byref(self._cfg), self.device, self._open_stream(), C.byref(o)), "bbb_nco_open")
         self._o = o
 
     @staticmethod
@@ -79,19 +79,10 @@ class NCO:
         _lib.check(_lib.lib().bbb_nco_set_cfg(self._o, C.byref(cfg)), "bbb_nco_set_cfg")
         self._cfg = cfg
 
-    def _bind_stream(self):
-        s = torch.cuda.current_stream(self.device).cuda_stream
-        if s != self._stream:
-            _lib.check(_lib.lib().bbb_nco_set_stream(self._o, C.c_void_p(s)), "bbb_nco_set_stream")
-            self._stream = s
-
     def _buf(self, name, t, dtype, nsamples):
         if t is None:
             return None
-        if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_cuda or t.dim() != 1 or not t.is_contiguous():
-            raise ValueError(f"{name} must be a contiguous 1-D {dtype} CUDA tensor")
-        if t.device != torch.device("cuda", self.device):
-            raise ValueError(f"{name} must be on cuda:{self.device}")
+        _lib.cuda_tensor(name, t, (dtype,), dtype, self.device)
         if t.numel() < nsamples:
             raise ValueError(f"{name} holds {t.numel()} values, the call needs {nsamples}")
         return t
@@ -195,20 +186,3 @@ class NCO:
         started at reset.  `taps`: a list of int16 with `shift`, or a fir.FIR."""
         from .ddc import DDC
         return DDC(self.fcw, taps, decim, phase, shift, pa0=(-3 * self.fcw) % (1 << 24), device=self.device)
-
-    def close(self):
-        o, self._o = getattr(self, "_o", None), None
-        if o:
-            _lib.check(_lib.lib().bbb_nco_close(o), "bbb_nco_close")
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

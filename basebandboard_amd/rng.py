@@ -265,9 +265,10 @@ class CLTGRNG:
         return out
 
 
-class SampleStream:
+class SampleStream(_lib.Handle):
     """bbb_awgn_stream_*: the CLTGRNG sample stream read sequentially.  Context manager; closing restores the
     generator handle's mode."""
+    _handle, _close = "_s", "bbb_awgn_stream_close"
 
     def __init__(self, grng, nsamples_per_call, first_step=0):
         self.grng = grng
@@ -309,20 +310,3 @@ class SampleStream:
         v = C.c_uint64()
         _lib.check(_lib.lib().bbb_awgn_stream_tell(self._s, C.byref(v)), "bbb_awgn_stream_tell")
         return v.value
-
-    def close(self):
-        s, self._s = getattr(self, "_s", None), None
-        if s:
-            _lib.check(_lib.lib().bbb_awgn_stream_close(s), "bbb_awgn_stream_close")
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

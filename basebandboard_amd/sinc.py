@@ -50,11 +50,7 @@ class SincInterpolator:
         return torch.device("cuda", self.device)
 
     def _check(self, samples, shift):
-        if (not isinstance(samples, torch.Tensor) or samples.dtype not in _DT or not samples.is_cuda or samples.dim() != 1
-                or not samples.is_contiguous()):
-            raise ValueError("samples must be a contiguous 1-D int8 or int16 CUDA tensor")
-        if samples.device != self._dev():
-            raise ValueError(f"samples must be on cuda:{self.device}")
+        _lib.cuda_tensor("samples", samples, _DT, "int8 or int16", self.device)
         shift = int(shift)
         if not 0 <= shift <= 15:
             raise ValueError("shift must be 0..15")
