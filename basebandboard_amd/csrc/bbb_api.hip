@@ -55,14 +55,16 @@ int use_device(int device) {
 
 namespace {
 
-// A hipEventDisableTiming event, created by its first record (a host-only handle creates none); the destructor destroys it.
+// An owned event; the destructor destroys it.  An ordering event (hipEventDisableTiming) is created by its first record, so
+// a host-only handle creates none; an event that bbb_lutopt_profile reads times between is created by create_timed().
 struct Event {
     hipEvent_t e = nullptr;
     Event() = default;
     Event(Event &&o) noexcept : e(o.e) { o.e = nullptr; }
-    Event &operator=(Event &&o) noexcept { std::swap(e, o.e); return *this; }
+    Event &operator=(Event &&o) noexcept { std::swap(e, o.e); return *this; }      // (o destroys the old one)
     ~Event() { if (e) (void)hipEventDestroy(e); }
     operator hipEvent_t() const { return e; }
+    int create_timed() { BBB_HIP(hipEventCreate(&e)); return BBB_OK; }
     int record(hipStream_t s) {
         if (!e) BBB_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
         BBB_HIP(hipEventRecord(e, s));
@@ -101,6 +103,66 @@ struct ReadGuarded {
     }
 };
 enum { kStates = 0, kPlanes = 1 };     // the two buffers of a set of generator start states
+
+// One of the two staging slots of the two-kernel ("staged") form (see queue_mover_with): the buffer a sample kernel fills and
+// its movers read, the events on either side of it, and the transmitter's data bits for the slot's windows.
+struct StageSlot {
+    DevBuf<uint32_t> stage;
+    Event arith;                  // recorded behind the sample kernel that filled the slot
+    Event free;                   // recorded behind the mover that read the buffer (behind ALL its movers: queue_mover_with)
+    bool busy = false;            // a mover has been queued since the buffer was last grown
+    uint64_t gen = 0;             // movers queued on the slot so far
+    // staged TX: the data bits of a noise kernel's windows, written on the slot's arithmetic stream in front of the sample kernel, read by the
+    // slot's movers.  TWO buffers, taken in turn (round 5): the bits of the slot's next kernel then do not wait for the movers of its last
+    // one -- only the sample kernel does, for the staging buffer itself -- and 55 us leave the gap between two noise kernels.  The
+    // readers of the buffer taken now are the movers of the slot's kernel BEFORE last, which the last kernel -- queued on this same stream --
+    // waited for.
+    DevBuf<uint32_t> bits[2];
+    unsigned bits_turn = 0;
+
+    // Growing frees the old buffer, so the host first synchronises with the slot's last mover, the last reader of all three
+    // buffers.  A new staging buffer has no mover; behind new data bits the staging buffer is still the last mover's: busy stays.
+    int grow_stage(size_t words) {
+        if (stage.cap >= words) return BBB_OK;
+        if (busy) BBB_HIP(hipEventSynchronize(free));
+        busy = false;
+        return stage.grow(words);
+    }
+    int grow_bits(unsigned b, size_t words) {
+        if (bits[b].cap >= words) return BBB_OK;
+        if (busy) BBB_HIP(hipEventSynchronize(free));
+        return bits[b].grow(words);
+    }
+    // whatever `s` queues next comes behind the slot's last mover
+    int wait_free(hipStream_t s) const { if (busy) BBB_HIP(hipStreamWaitEvent(s, free, 0)); return BBB_OK; }
+    int mover_queued(hipStream_t ms) {
+        if (const int rc = free.record(ms)) return rc;
+        busy = true;
+        gen++;
+        return BBB_OK;
+    }
+};
+
+// A set of start states seeded ahead of the kernel that reads it, for stream position (first, L, G): the handle's second set for an
+// announced fill (bbb_awgn_prefetch), and the two sets of the BER trials (ber_run).  set.last_read: behind the kernel that last
+// read them; seeded: behind the seeding that filled them, on whatever stream that went to
+struct SeededStates {
+    bool valid = false;
+    uint64_t first = 0, L = 0, G = 0;
+    ReadGuarded<2> set;
+    Event seeded;
+    bool matches(uint64_t f, uint64_t l, uint64_t g) const { return valid && first == f && L == l && G == g; }
+};
+
+// the three events bbb_lutopt_profile puts around a timed call: in front of its start states, of its sample kernel, behind it
+struct ProfEv {
+    Event e0, e1, e2;
+    int begin(hipStream_t s) {      // (created together, where the call starts)
+        for (Event *e : {&e0, &e1, &e2})
+            if (const int rc = e->create_timed()) return rc;
+        return e0.record(s);
+    }
+};
 
 }  // namespace
 
@@ -148,22 +210,10 @@ struct bbb_lutopt {
     // kernel of call s still reads its own -- two buffers, each with the event of its last reader
     ReadGuarded<1> fbits[2];
     Event fbits_ready;
-    // staged TX: the data bits of a noise kernel's windows, written on the staging slot's arithmetic stream in front of the sample kernel, read by the
-    // slot's movers.  TWO buffers per slot, taken in turn (round 5): the bits of the slot's next kernel then do not wait for the movers of its last
-    // one -- only the sample kernel does, for the staging slot itself -- and 55 us leave the gap between two noise kernels.  The readers
-    // of the buffer taken now are the movers of the slot's kernel BEFORE last, which the last kernel -- queued on this same stream -- waited for.
-    // (Their last reader is the slot's: a grow synchronises with stage_free.)
-    DevBuf<uint32_t> d_mbits[2][2];
-    unsigned mbits_turn[2] = {0, 0};
-    // BER trials (round 5): the generators' start states from awgn_seed_head_launch / _tail_planes_launch (two launches: the first 65536 states packed,
-    // u32[8][65536], then the planes [256][nlanes] directly), two buffer pairs taken in turn like the PRBS pairs; bs_read[b]: behind the
-    // trial kernel that last read pair b; bs_ready[b]: behind the seeding that filled it (on the caller's stream or an arithmetic one)
-    // (kept as parallel arrays: tests/test_sched_model.py's mutant "ber_buffer_reuse" takes the pair's read wait out by its text)
-    DevBuf<uint32_t> d_bstates[2], d_bplanes[2];
-    Event bs_read[2], bs_ready[2];
-    bool bs_pending[2] = {false, false}, bs_valid[2] = {false, false};
-    uint64_t bs_first[2] = {0, 0}, bs_L[2] = {0, 0}, bs_G[2] = {0, 0};
-    int bs_idx = 0;
+    // the generators' start states of a BER trial (awgn_seed_head_launch / _tail_planes_launch: the first 65536 states packed,
+    // u32[8][65536], then the planes [256][nlanes]), two sets taken in turn like the PRBS pairs (ber_run)
+    SeededStates seeds[2];
+    int seeds_idx = 0;
     DevBuf<unsigned long long, true> h_counters;     // pinned: the read-back of bbb_ber_trials / bbb_ber_sweep_multi
     // d_counters is zeroed BEHIND the read-back of the call that used it (counters_zeroed: the event behind that memset), so that the
     // next call's seeding is the first thing it queues; a call on another stream waits for the event
@@ -176,17 +226,7 @@ struct bbb_lutopt {
     unsigned max_waves = 1024;
     // prefetched start states for an announced next fill (bbb_awgn_prefetch): seeded on a side stream
     // while the previous sample kernel runs, swapped in by the matching bbb_awgn_fill_i8
-    struct Prefetch {
-        bool valid = false;
-        uint64_t first = 0, L = 0, G = 0;
-        unsigned nlanes = 0;
-        ReadGuarded<2> set;               // the second set of start-state buffers (as cur)
-        // recorded on the side stream after seeding; created by the first seeding (seed_announced, whose wait for it
-        // tests/test_sched_model.py's mutant "untaken_hint" takes out by its text)
-        hipEvent_t seeded = nullptr;
-        ~Prefetch() { if (seeded) (void)hipEventDestroy(seeded); }
-        bool matches(uint64_t f, uint64_t l, uint64_t g) const { return valid && first == f && L == l && G == g; }
-    } pf;
+    SeededStates pf;                      // (its set: the second set of start-state buffers, as cur; seed_announced)
     hipStream_t side = nullptr;
     // The stream the library's plane-touching work of the current call goes to: the caller's stream, or -- for the
     // two-kernel ("staged") form of the sample stream -- an internal one, so that the next fill's arithmetic does
@@ -195,21 +235,17 @@ struct bbb_lutopt {
     bool cs_valid = false;
     Event handover;
     bool staged_mode = false;             // bbb_lutopt_set_staged
-    bool has_stream = false;              // a bbb_awgn_stream is open on this handle
+    bool has_stream = false;              // a bbb_awgn_stream or a bbb_tx_stream is open on this handle (SeqStream)
     // internal streams: arithmetic (one per staging slot: consecutive sample kernels go to alternate streams, so that the
     // barrier packets in front of kernel s+1 -- the wait for its start states, the record behind kernel s -- are
     // processed while kernel s still runs instead of between the two: 21-27 us per step in profiles/r03_ramp_clock_per_launch.log)
     // and the piece mover
     hipStream_t xs2[2] = {nullptr, nullptr}, ys = nullptr;
-    DevBuf<uint32_t> d_stage[2];
-    Event stage_free[2];                  // recorded behind the mover that read the buffer (behind ALL its movers: queue_mover_with)
-    bool stage_busy[2] = {false, false};
-    int stage_slot = 0;
+    StageSlot slots[2];
+    int stage_slot = 0;                   // the slot the last sample kernel took
     Event ev_user;
     int pf_waited_slot = -1;              // staging slot whose mover the pending prefetch's seeding waited for
-    uint64_t stage_gen[2] = {0, 0};       // movers queued on the slot so far
-    uint64_t pf_waited_gen = 0;           // stage_gen[pf_waited_slot] when that seeding was queued: a later mover voids the skip
-    Event stage_arith[2];                 // recorded behind the sample kernel that filled the slot
+    uint64_t pf_waited_gen = 0;           // slots[pf_waited_slot].gen when that seeding was queued: a later mover voids the skip
     // look-ahead (bbb_lutopt_set_staged(h, m), m >= 2): the sample kernel of a fill also produced the next m - 1 fills'
     // samples, which wait in its staging slot: `left` more fills of n samples, the next one at stream position `first`
     // (kind 0: bbb_awgn_fill_i8, a generator step; kind 1: bbb_tx_fill_i16 with configuration `cfg`, a TX sample index)
@@ -225,11 +261,10 @@ struct bbb_lutopt {
     int staged_level = 0;                 // 0 off, 1 staged, m >= 2 staged with m fills per sample kernel
     // optional per-call device timing of the generator kernels (bbb_lutopt_profile)
     bool profiling = false;
-    struct ProfEv { hipEvent_t e0, e1, e2; };
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_mover_pending;      // around every mover, on its stream
+    std::vector<std::pair<Event, Event>> prof_mover_pending;      // around every mover, on its stream
     double prof_mover_ms = 0; uint64_t prof_mover_calls = 0;
     std::vector<ProfEv> prof_pending;
-    hipEvent_t prof_prev_e2 = nullptr;    // completion of the last sample kernel bbb_lutopt_profile_read has accounted for
+    Event prof_prev_e2;                   // completion of the last sample kernel bbb_lutopt_profile_read has accounted for
     double prof_seed_ms = 0, prof_main_ms = 0;
     uint64_t prof_calls = 0;
 };
@@ -532,6 +567,7 @@ int acquire_planes(bbb_lutopt *h, uint64_t first_step, uint64_t L, uint64_t G, u
 template <typename LaunchMover>
 int queue_mover_with(bbb_lutopt *h, int slot, LaunchMover launch_mover) {
     hipStream_t ms = h->stream;
+    StageSlot &sl = h->slots[slot];
     int rc;
     // (-DBBB_EXPERIMENTS, BBB_EXP_MOVER_OWN_STREAM=1: rounds 2-4's mover on a fourth internal stream tied to the caller's by an
     // event each way, for the A/B of experiments/mover_stream_ab.py)
@@ -542,26 +578,24 @@ int queue_mover_with(bbb_lutopt *h, int slot, LaunchMover launch_mover) {
         if ((rc = h->ev_user.record(h->stream))) return rc;
         BBB_HIP(hipStreamWaitEvent(ms, h->ev_user, 0));
     }
-    BBB_HIP(hipStreamWaitEvent(ms, h->stage_arith[slot], 0));
-    // stage_free[slot] stands for ALL movers that read the slot: the caller may have re-bound the handle to another stream since
+    BBB_HIP(hipStreamWaitEvent(ms, sl.arith, 0));
+    // The slot's free event stands for ALL movers that read it: the caller may have re-bound the handle to another stream since
     // the slot's previous mover, so that one is chained in front of this call's record (same stream: already in its past).
     // (tests/test_sched_model.py takes this line out of a COPY of this file -- mutant "mover_chain" -- and requires the model to find
     // a sample kernel overwriting a slot that a mover on the caller's OTHER stream still reads)
-    if (h->stage_busy[slot]) BBB_HIP(hipStreamWaitEvent(ms, h->stage_free[slot], 0));
-    hipEvent_t m0 = nullptr, m1 = nullptr;
+    if ((rc = sl.wait_free(ms))) return rc;
+    Event m0, m1;
     if (h->profiling) {
-        BBB_HIP(hipEventCreate(&m0)); BBB_HIP(hipEventCreate(&m1));
+        if ((rc = m0.create_timed()) || (rc = m1.create_timed())) return rc;
         BBB_HIP(hipEventRecord(m0, ms));
     }
-    if ((rc = launch_mover((const void *)h->d_stage[slot].p, ms))) return rc;
+    if ((rc = launch_mover((const void *)sl.stage.p, ms))) return rc;
     if (h->profiling) {
         BBB_HIP(hipEventRecord(m1, ms));
-        h->prof_mover_pending.emplace_back(m0, m1);
+        h->prof_mover_pending.emplace_back(std::move(m0), std::move(m1));
     }
-    if ((rc = h->stage_free[slot].record(ms))) return rc;
-    h->stage_busy[slot] = true;
-    h->stage_gen[slot]++;
-    if (own_stream) BBB_HIP(hipStreamWaitEvent(h->stream, h->stage_free[slot], 0));
+    if ((rc = sl.mover_queued(ms))) return rc;
+    if (own_stream) BBB_HIP(hipStreamWaitEvent(h->stream, sl.free, 0));
     return BBB_OK;
 }
 
@@ -611,32 +645,27 @@ uint64_t ahead_total(const bbb_lutopt *h, uint64_t n, uint64_t cap, uint64_t ste
 // produce: the sample kernel for the stream positions the planes in h->cur describe, L steps per generator, into the
 // next staging slot.  planes_seeded_after_mover: the start states came from a prefetch whose seeding had itself waited for
 // the mover that last read this slot (bbb_awgn_prefetch on a staged handle), so the arithmetic need not wait for it again.
-int produce_planes(bbb_lutopt *h, uint64_t L, unsigned nlanes, bbb_lutopt::ProfEv *ev, bool planes_seeded_after_mover, int *slot_out,
+int produce_planes(bbb_lutopt *h, uint64_t L, unsigned nlanes, ProfEv *ev, bool planes_seeded_after_mover, int *slot_out,
                    bool small_footprint = false) {
-    const size_t need_words = stage_words(nlanes, L);
     const int slot = h->stage_slot ^= 1;
+    StageSlot &sl = h->slots[slot];
     *slot_out = slot;
     if (h->ahead.valid && h->ahead.slot == slot) h->ahead.valid = false;            // what waited there is overwritten now
     int rc;
-    if (h->d_stage[slot].cap < need_words) {
-        if (h->stage_busy[slot]) BBB_HIP(hipEventSynchronize(h->stage_free[slot]));     // growing frees the old buffer
-        h->stage_busy[slot] = false;
-        if ((rc = h->d_stage[slot].grow(need_words))) return rc;
-    }
+    if ((rc = sl.grow_stage(stage_words(nlanes, L)))) return rc;
     // (the skip holds only while no LATER mover was queued on the slot: a prefetch stays valid across fills that do not
     // match it, and those may have put new movers on this very slot since its seeding waited)
     // (the round-2 advisor's case; tests/test_sched_model.py's mutant "stale_skip" drops the generation check from a copy of this file)
-    const bool seeding_saw_last_mover = planes_seeded_after_mover && h->pf_waited_slot == slot && h->pf_waited_gen == h->stage_gen[slot];
+    const bool seeding_saw_last_mover = planes_seeded_after_mover && h->pf_waited_slot == slot && h->pf_waited_gen == sl.gen;
     if (planes_seeded_after_mover) h->pf_waited_slot = -1;          // consumed
-    if (h->stage_busy[slot] && !seeding_saw_last_mover)
-        BBB_HIP(hipStreamWaitEvent(h->cs, h->stage_free[slot], 0));   // its last mover has read it
+    if (!seeding_saw_last_mover && (rc = sl.wait_free(h->cs))) return rc;         // its last mover has read it
     if (ev) BBB_HIP(hipEventRecord(ev->e1, h->cs));
-    rc = awgn256_planes_launch(h->cur.buf[kPlanes], (void *)h->d_stage[slot].p, (unsigned)L, nlanes, h->cs, small_footprint);
+    rc = awgn256_planes_launch(h->cur.buf[kPlanes], (void *)sl.stage.p, (unsigned)L, nlanes, h->cs, small_footprint);
     h->last_staged_small = small_footprint;
     if (rc) return rc;
     if ((rc = mark_planes_read(h))) return rc;
     if (ev) BBB_HIP(hipEventRecord(ev->e2, h->cs));
-    return h->stage_arith[slot].record(h->cs);
+    return sl.arith.record(h->cs);
 }
 
 struct StagedRun { uint64_t L = 0, G = 0; unsigned nlanes = 0; int slot = 0; };      // a staged sample kernel's partition and its slot
@@ -657,18 +686,15 @@ int staged_produce(bbb_lutopt *h, uint64_t ntotal, uint64_t seed_step, bool smal
     int rc = begin_op(h, true, h->pf.matches(seed_step, L, G));
     if (rc) return rc;
     h->last_fill_tx = false;            // (what runs on the SIMDs is the plain kernel)
-    bbb_lutopt::ProfEv ev{};
+    ProfEv ev;
     const bool prof = timed && h->profiling;
-    if (prof) {
-        BBB_HIP(hipEventCreate(&ev.e0)); BBB_HIP(hipEventCreate(&ev.e1)); BBB_HIP(hipEventCreate(&ev.e2));
-        BBB_HIP(hipEventRecord(ev.e0, h->cs));
-    }
+    if (prof && (rc = ev.begin(h->cs))) return rc;
     bool from_pf = false;
     if ((rc = acquire_planes(h, seed_step, L, G, r.nlanes, true, &from_pf))) return rc;
     if ((rc = hook())) return rc;
     rc = produce_planes(h, L, r.nlanes, prof ? &ev : nullptr, from_pf, &r.slot, small_form);
     if (!rc) rc = queue_mover_with(h, r.slot, [&](const void *stage, hipStream_t ms) { return launch_mover(r, stage, ms); });
-    if (prof) h->prof_pending.push_back(ev);
+    if (prof) h->prof_pending.push_back(std::move(ev));
     return rc;
 }
 
@@ -746,11 +772,8 @@ int awgn_fill(bbb_lutopt *h, void *dst, int elem_size, uint64_t nsamples, uint64
     }
     int rc = begin_op(h, false);
     if (rc) return rc;
-    bbb_lutopt::ProfEv ev{};
-    if (h->profiling) {
-        BBB_HIP(hipEventCreate(&ev.e0)); BBB_HIP(hipEventCreate(&ev.e1)); BBB_HIP(hipEventCreate(&ev.e2));
-        BBB_HIP(hipEventRecord(ev.e0, h->cs));
-    }
+    ProfEv ev;                              // (only the specialised kernel is timed: every other way out drops the events)
+    if (h->profiling && (rc = ev.begin(h->cs))) return rc;
     rc = acquire_planes(h, first_step, L, G, nlanes, fast256);
     if (rc) return rc;
     if (fast256) {
@@ -759,11 +782,10 @@ int awgn_fill(bbb_lutopt *h, void *dst, int elem_size, uint64_t nsamples, uint64
         if (!rc) rc = mark_planes_read(h);
         if (h->profiling) {
             BBB_HIP(hipEventRecord(ev.e2, h->cs));
-            h->prof_pending.push_back(ev);
+            h->prof_pending.push_back(std::move(ev));
         }
         return rc;
     }
-    if (h->profiling) { (void)hipEventDestroy(ev.e0); (void)hipEventDestroy(ev.e1); (void)hipEventDestroy(ev.e2); }
     if (h->custom_fill && elem_size == 1) {
         const int e = h->custom_fill(h->cur.buf[kPlanes], (int8_t *)dst, nsamples, (uint32_t)L, G, nlanes, (void *)h->cs);
         if (e) return fail(BBB_EHIP, std::string("custom sample kernel: ") + hipGetErrorString((hipError_t)e));
@@ -898,18 +920,14 @@ int ber_run(bbb_lutopt *h, const bbb_trial_cfg *cfgs, int ncfg, unsigned long lo
         }
         int sb = -1;
         for (int b : {0, 1})
-            if (h->bs_valid[b] && h->bs_first[b] == gen_first && h->bs_L[b] == L && h->bs_G[b] == G) sb = b;     // (the same trial again)
+            if (h->seeds[b].matches(gen_first, L, G)) sb = b;     // (the same trial again)
         const bool seed_gen = sb < 0;
         if (seed_gen) {
-            sb = h->bs_idx ^= 1;
+            sb = h->seeds_idx ^= 1;
+            const size_t need[2] = {(size_t)65536 * h->W32, (size_t)h->k * nlanes};
             for (int b : {sb, sb ^ 1}) {
-                if (h->d_bstates[b].cap < (size_t)65536 * h->W32 || h->d_bplanes[b].cap < (size_t)h->k * nlanes) {
-                    if (h->bs_pending[b]) BBB_HIP(hipEventSynchronize(h->bs_read[b]));      // growing frees the old buffers
-                    h->bs_pending[b] = false;
-                    h->bs_valid[b] = false;
-                    if ((rc = h->d_bstates[b].grow((size_t)65536 * h->W32))) return rc;
-                    if ((rc = h->d_bplanes[b].grow((size_t)h->k * nlanes))) return rc;
-                }
+                if (!h->seeds[b].set.fits(need)) h->seeds[b].valid = false;      // (new buffers hold no trial's states)
+                if ((rc = h->seeds[b].set.grow(need))) return rc;
             }
             if ((rc = get_plan(h, L, &plan))) return rc;
             if ((rc = ensure_top_tables(plan))) return rc;
@@ -921,32 +939,32 @@ int ber_run(bbb_lutopt *h, const bbb_trial_cfg *cfgs, int ncfg, unsigned long lo
         ReadGuarded<1> &prbs = h->pp[pb];
         // (the PRBS pair's last reader, the trial before last: wherever its seeding goes now)
         if ((rc = prbs.wait_read(seed_gen ? ss : h->cs))) return rc;
+        SeededStates &gs = h->seeds[sb];
         if (seed_gen) {
-            h->bs_valid[sb] = false;
-            if (h->bs_pending[sb]) BBB_HIP(hipStreamWaitEvent(ss, h->bs_read[sb], 0));    // the trial before last read this pair
+            gs.valid = false;
+            if ((rc = gs.set.wait_read(ss))) return rc;    // the trial before last read this set
             // the PRBS start states ride on the head launch (extra blocks: VALU work beside the head's LDS and L2 latency)
             const PrbsSeedRide ride{c.prbs_k, pp->d_cols, ps16, pp->qcol64, nlanes, prbs.buf[0]};
-            if ((rc = awgn_seed_head_launch(h->k, plan->d_cols, s16, G, h->d_bstates[sb], ss, &ride))) return rc;
-            if ((rc = awgn_seed_tail_planes_launch(h->k, plan->d_top, G, h->d_bstates[sb], nlanes, h->d_bplanes[sb], ss))) return rc;
-            if ((rc = h->bs_ready[sb].record(ss))) return rc;
-            if (busy) BBB_HIP(hipStreamWaitEvent(h->cs, h->bs_ready[sb], 0));
-            h->bs_valid[sb] = true;
-            h->bs_first[sb] = gen_first; h->bs_L[sb] = L; h->bs_G[sb] = G;
+            if ((rc = awgn_seed_head_launch(h->k, plan->d_cols, s16, G, gs.set.buf[kStates], ss, &ride))) return rc;
+            if ((rc = awgn_seed_tail_planes_launch(h->k, plan->d_top, G, gs.set.buf[kStates], nlanes, gs.set.buf[kPlanes], ss))) return rc;
+            if ((rc = gs.seeded.record(ss))) return rc;
+            if (busy) BBB_HIP(hipStreamWaitEvent(h->cs, gs.seeded, 0));
+            gs.valid = true;
+            gs.first = gen_first; gs.L = L; gs.G = G;
         } else {
             // the same trial again: its generator states were derived by an earlier call -- on whatever stream that call found right;
             // the PRBS states (their pairs alternate) in line
-            BBB_HIP(hipStreamWaitEvent(h->cs, h->bs_ready[sb], 0));
+            BBB_HIP(hipStreamWaitEvent(h->cs, gs.seeded, 0));
             if ((rc = prbs_seed_lanes_launch(c.prbs_k, pp->d_cols, ps16, pp->qcol64, G, nlanes, prbs.buf[0], h->cs))) return rc;
         }
         if (h->specialised) {
-            if ((rc = ber256_launch(h->d_bplanes[sb], prbs.buf[0], &td[(size_t)i], n, nlanes, counters_dev + 2 * (size_t)i, h->cs))) return rc;
+            if ((rc = ber256_launch(gs.set.buf[kPlanes], prbs.buf[0], &td[(size_t)i], n, nlanes, counters_dev + 2 * (size_t)i, h->cs))) return rc;
         } else {
-            const int e = h->custom_ber(h->d_bplanes[sb], prbs.buf[0], &td[(size_t)i], n, nlanes, (uint64_t *)(counters_dev + 2 * (size_t)i), (void *)h->cs);
+            const int e = h->custom_ber(gs.set.buf[kPlanes], prbs.buf[0], &td[(size_t)i], n, nlanes, (uint64_t *)(counters_dev + 2 * (size_t)i), (void *)h->cs);
             if (e) return fail(e < 0 ? e : BBB_EHIP, "custom BER kernel failed");
         }
         if ((rc = prbs.mark_read(h->cs))) return rc;
-        if ((rc = h->bs_read[sb].record(h->cs))) return rc;
-        h->bs_pending[sb] = true;
+        if ((rc = gs.set.mark_read(h->cs))) return rc;
         i += n;
     }
     return BBB_OK;
@@ -1074,12 +1092,14 @@ int bbb_lutopt_destroy(bbb_lutopt *h) {
     if (h->device < 0) { delete h; return BBB_OK; }
     (void)hipSetDevice(h->device);
     (void)hipDeviceSynchronize();
-    // (profiling events of calls whose times were never read: found by the scheduler model's leak check, tests/sched_model)
-    for (auto &pr : h->prof_mover_pending) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
-    for (auto &ev : h->prof_pending) { (void)hipEventDestroy(ev.e0); (void)hipEventDestroy(ev.e1); (void)hipEventDestroy(ev.e2); }
-    if (h->prof_prev_e2) (void)hipEventDestroy(h->prof_prev_e2);
     if (h->ys) (void)hipStreamDestroy(h->ys);        // (the other internal streams are the device's pool: ensure_internal_streams)
-    delete h;                                        // (its members free the device buffers and destroy the events)
+    // (the staging buffers, the prefetch set and the trial seeds first, each kind from the second to the first: the order in
+    // which the handle has always freed them, ahead of the slots' data bits and everything declared before them)
+    for (int s : {1, 0}) h->slots[s].stage = {};
+    for (int i : {kPlanes, kStates}) h->pf.set.buf[i] = {};
+    for (int i : {kPlanes, kStates})
+        for (int b : {1, 0}) h->seeds[b].set.buf[i] = {};
+    delete h;                                        // (its members free the other device buffers and destroy the events)
     return BBB_OK;
 }
 
@@ -1144,7 +1164,9 @@ int bbb_lutopt_profile(bbb_lutopt *h, int enable) {
 
 int bbb_lutopt_profile_read(bbb_lutopt *h, double *seed_ms, double *kernel_ms, uint64_t *calls, int reset) {
     if (!h) return fail(BBB_EINVAL, "null handle");
-    for (auto &ev : h->prof_pending) {
+    std::vector<ProfEv> pending;          // (taken: read once, and on every way out their events go with them)
+    pending.swap(h->prof_pending);
+    for (ProfEv &ev : pending) {
         BBB_HIP(hipEventSynchronize(ev.e2));
         float a = 0, b = 0;
         BBB_HIP(hipEventElapsedTime(&a, ev.e0, ev.e1));
@@ -1156,13 +1178,10 @@ int bbb_lutopt_profile_read(bbb_lutopt *h, double *seed_ms, double *kernel_ms, u
             float c = 0;
             BBB_HIP(hipEventElapsedTime(&c, h->prof_prev_e2, ev.e2));
             if (c > 0 && c < b) b = c;
-            (void)hipEventDestroy(h->prof_prev_e2);
         }
-        h->prof_prev_e2 = ev.e2;
+        h->prof_prev_e2 = std::move(ev.e2);
         h->prof_seed_ms += a; h->prof_main_ms += b; h->prof_calls++;
-        (void)hipEventDestroy(ev.e0); (void)hipEventDestroy(ev.e1);
     }
-    h->prof_pending.clear();
     if (seed_ms) *seed_ms = h->prof_seed_ms;
     if (kernel_ms) *kernel_ms = h->prof_main_ms;
     if (calls) *calls = h->prof_calls;
@@ -1172,14 +1191,14 @@ int bbb_lutopt_profile_read(bbb_lutopt *h, double *seed_ms, double *kernel_ms, u
 
 int bbb_lutopt_profile_read_mover(bbb_lutopt *h, double *mover_ms, uint64_t *calls, int reset) {
     if (!h) return fail(BBB_EINVAL, "null handle");
-    for (auto &ev : h->prof_mover_pending) {
+    std::vector<std::pair<Event, Event>> pending;      // (taken, as in bbb_lutopt_profile_read)
+    pending.swap(h->prof_mover_pending);
+    for (const auto &ev : pending) {
         BBB_HIP(hipEventSynchronize(ev.second));
         float a = 0;
         BBB_HIP(hipEventElapsedTime(&a, ev.first, ev.second));
         h->prof_mover_ms += a; h->prof_mover_calls++;
-        (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second);
     }
-    h->prof_mover_pending.clear();
     if (mover_ms) *mover_ms = h->prof_mover_ms;
     if (calls) *calls = h->prof_mover_calls;
     if (reset) { h->prof_mover_ms = 0; h->prof_mover_calls = 0; }
@@ -1199,7 +1218,7 @@ static int seed_announced(bbb_lutopt *h, uint64_t first_step, uint64_t L, uint64
     JumpPlan *plan;
     int rc = get_plan(h, L, &plan);
     if (rc) return rc;
-    bbb_lutopt::Prefetch &pf = h->pf;
+    SeededStates &pf = h->pf;
     pf.valid = false;
     // An announcement that was never taken leaves its seeding behind -- queued on the arithmetic stream of the fill it expected,
     // which need not be the one this seeding goes to: without this wait the two would write the same buffers side by side
@@ -1207,7 +1226,6 @@ static int seed_announced(bbb_lutopt *h, uint64_t first_step, uint64_t L, uint64
     // (tests/test_sched_model.py's mutant "untaken_hint" is a copy of this file as it stood BEFORE this wait existed: the model of
     // tests/sched_model/ must find that race)
     if (pf.seeded) BBB_HIP(hipStreamWaitEvent(side, pf.seeded, 0));
-    else BBB_HIP(hipEventCreateWithFlags(&pf.seeded, hipEventDisableTiming));
     // the buffers may still be read by the sample kernel that used them last (main stream)
     if ((rc = pf.set.wait_read(side))) return rc;
     if ((rc = pf.set.grow({(size_t)G * h->W32, (size_t)2 * h->k * nlanes}))) return rc;
@@ -1215,9 +1233,9 @@ static int seed_announced(bbb_lutopt *h, uint64_t first_step, uint64_t L, uint64
     uint32_t s16[256];
     first16_at(h, *plan, first_step, s16);
     if ((rc = awgn_seed_launch(h->k, plan->d_cols, s16, G, pf.set.buf[kStates], G, nlanes, pf.set.buf[kPlanes], side, h->fast512 ? 1 : 0, seed_variant))) return rc;
-    BBB_HIP(hipEventRecord(pf.seeded, side));
+    if ((rc = pf.seeded.record(side))) return rc;
     pf.valid = true;
-    pf.first = first_step; pf.L = L; pf.G = G; pf.nlanes = nlanes;
+    pf.first = first_step; pf.L = L; pf.G = G;
     return BBB_OK;
 }
 
@@ -1283,10 +1301,11 @@ static int awgn_prefetch(bbb_lutopt *h, uint64_t nsamples, uint64_t first_step, 
     h->pf_waited_slot = -1;
     h->pf.valid = false;
     // (Beside the small form of the sample kernel -- the transmitter's -- there is room for both guests at once.)
-    if (h->staged_mode && h->stage_busy[h->stage_slot ^ 1] && !h->last_staged_small) {
-        BBB_HIP(hipStreamWaitEvent(side, h->stage_free[h->stage_slot ^ 1], 0));
+    const StageSlot &next = h->slots[h->stage_slot ^ 1];
+    if (h->staged_mode && next.busy && !h->last_staged_small) {
+        if ((rc = next.wait_free(side))) return rc;
         h->pf_waited_slot = h->stage_slot ^ 1;
-        h->pf_waited_gen = h->stage_gen[h->stage_slot ^ 1];
+        h->pf_waited_gen = next.gen;
     }
     // (this seeding runs beside the kernel of the fill before: the transmitter variant leaves LDS for 8 KiB pieces only)
     return seed_announced(h, first_step, L, G, nlanes, side, h->last_fill_tx ? 4 : 2);
@@ -1308,73 +1327,58 @@ int bbb_awgn_fill_i16(bbb_lutopt *h, int16_t *dst_dev, uint64_t nsamples, uint64
     return awgn_fill(h, dst_dev, 2, nsamples, first_step);
 }
 
-/* ---- the sample stream as an object (include/bbb.h) ------------------------------------------------------------ */
+/* ---- the two sequential-stream objects (include/bbb.h): the sample stream and the transmitter's waveform ----------- */
 
-struct bbb_awgn_stream {
+// A reader that takes one handle's stream in equal calls, one after the other: it gets the staged form with look-ahead and
+// announced start states without choreographing bbb_lutopt_set_staged / bbb_awgn_prefetch itself.  The two objects differ in
+// the fill they call and in the announcement ("hint") they send for the next whole read; `what` in the refusal texts is the
+// name of their position argument (first_step / first_sample).
+struct SeqStream {
     bbb_lutopt *h = nullptr;
     uint64_t n = 0, pos = 0;
-    int elem = 1;
     int saved_level = 0;          // the handle's bbb_lutopt_set_staged level before the stream was opened
+    virtual ~SeqStream() = default;
+    virtual int fill(void *dst_dev, uint64_t nsamples) = 0;      // nsamples from pos
+    virtual int hint() = 0;                                      // the next read is expected to be n from pos
+    static int overflows(const char *what) { return fail(BBB_EINVAL, std::string(what) + " + nsamples_per_call overflows"); }
+
+    // the refusals every open ends with, the staging level (`level2`: two reads per sample kernel unless the caller chose a
+    // level), the first announcement, the claim on the handle
+    int open(bbb_lutopt *handle, uint64_t nsamples_per_call, uint64_t first, const char *what, bool level2) {
+        if (handle->has_stream) return fail(BBB_EINVAL, "the handle already has an open stream");
+        if (first + nsamples_per_call < first) return overflows(what);
+        h = handle; n = nsamples_per_call; pos = first;
+        saved_level = h->staged_level;
+        int rc;
+        if (h->staged_level == 0 && level2 && (rc = bbb_lutopt_set_staged(h, 2))) return rc;
+        if ((rc = hint())) return rc;
+        h->has_stream = true;
+        return BBB_OK;
+    }
+    int read(void *dst_dev, uint64_t nsamples) {
+        if (pos + nsamples < pos) return fail(BBB_EINVAL, "the stream position overflows");
+        const int rc = fill(dst_dev, nsamples);
+        if (rc) return rc;
+        pos += nsamples;
+        return hint();            // derived now, beside this read's kernels
+    }
+    int seek(uint64_t first, const char *what) {
+        if (first + n < first) return overflows(what);
+        pos = first;
+        h->ahead.valid = false;   // what a sample kernel produced ahead at the old position is dropped
+        return hint();
+    }
 };
 
-int bbb_awgn_stream_open(bbb_lutopt *h, uint64_t nsamples_per_call, uint64_t first_step, int elem_bytes, bbb_awgn_stream **out) {
-    if (!h || !out) return fail(BBB_EINVAL, "null argument");
-    if (nsamples_per_call == 0) return fail(BBB_EINVAL, "nsamples_per_call must be positive");
-    if (elem_bytes != 1 && elem_bytes != 2) return fail(BBB_EINVAL, "elem_bytes must be 1 (int8) or 2 (int16)");
-    if (h->device < 0) return fail(BBB_ENODEV, "host-only handle (device -1) cannot generate samples");
-    if (h->k & (h->k - 1)) return fail(BBB_EUNSUP, "CLTGRNG needs k to be a power of two (rng.py:72-76)");
-    if (elem_bytes == 1 && h->k > 256) return fail(BBB_EUNSUP, "k > 256 needs the int16 output");
-    if (h->has_stream) return fail(BBB_EINVAL, "the handle already has an open stream");
-    if (first_step + nsamples_per_call < first_step) return fail(BBB_EINVAL, "first_step + nsamples_per_call overflows");
-    std::unique_ptr<bbb_awgn_stream> s(new bbb_awgn_stream);
-    s->h = h; s->n = nsamples_per_call; s->pos = first_step; s->elem = elem_bytes;
-    s->saved_level = h->staged_level;
-    if (h->staged_level == 0) {            // (a caller who chose a level keeps it)
-        // two reads per sample kernel (look-ahead 2): a sequential reader is exactly the consumer that level is for, and it
-        // halves the start-state derivations -- beside the sample kernel the guests (mover, then seeding) otherwise take
-        // about as long as the kernel itself (same box, 1e9 per read: 1.16 ms per read at level 1, 1.055 at 2, 1.09 at 4)
-        int rc = bbb_lutopt_set_staged(h, 2);
-        if (rc) return rc;
-    }
-    int rc = bbb_awgn_prefetch(h, s->n, s->pos);
-    if (rc) return rc;
-    h->has_stream = true;
-    *out = s.release();
+static int seq_read(SeqStream *s, void *dst_dev, uint64_t nsamples) { return s && s->h ? s->read(dst_dev, nsamples) : fail(BBB_EINVAL, "null stream"); }
+static int seq_next(SeqStream *s, void *dst_dev) { return s ? seq_read(s, dst_dev, s->n) : fail(BBB_EINVAL, "null stream"); }
+static int seq_seek(SeqStream *s, uint64_t first, const char *what) { return s && s->h ? s->seek(first, what) : fail(BBB_EINVAL, "null stream"); }
+static int seq_tell(const SeqStream *s, uint64_t *next) {
+    if (!s || !next) return fail(BBB_EINVAL, "null argument");
+    *next = s->pos;
     return BBB_OK;
 }
-
-int bbb_awgn_stream_read(bbb_awgn_stream *s, void *dst_dev, uint64_t nsamples) {
-    if (!s || !s->h) return fail(BBB_EINVAL, "null stream");
-    if (s->pos + nsamples < s->pos) return fail(BBB_EINVAL, "the stream position overflows");
-    bbb_lutopt *h = s->h;
-    int rc = s->elem == 1 ? bbb_awgn_fill_i8(h, (int8_t *)dst_dev, nsamples, s->pos) : bbb_awgn_fill_i16(h, (int16_t *)dst_dev, nsamples, s->pos);
-    if (rc) return rc;
-    s->pos += nsamples;
-    // the next read is expected to be a whole one: its start states are derived now, beside this read's kernels
-    if (s->pos + s->n >= s->pos) rc = bbb_awgn_prefetch(h, s->n, s->pos);
-    return rc;
-}
-
-int bbb_awgn_stream_next(bbb_awgn_stream *s, void *dst_dev) {
-    if (!s) return fail(BBB_EINVAL, "null stream");
-    return bbb_awgn_stream_read(s, dst_dev, s->n);
-}
-
-int bbb_awgn_stream_seek(bbb_awgn_stream *s, uint64_t first_step) {
-    if (!s || !s->h) return fail(BBB_EINVAL, "null stream");
-    if (first_step + s->n < first_step) return fail(BBB_EINVAL, "first_step + nsamples_per_call overflows");
-    s->pos = first_step;
-    s->h->ahead.valid = false;            // what a sample kernel produced ahead at the old position is dropped
-    return bbb_awgn_prefetch(s->h, s->n, s->pos);
-}
-
-int bbb_awgn_stream_tell(const bbb_awgn_stream *s, uint64_t *next_step) {
-    if (!s || !next_step) return fail(BBB_EINVAL, "null argument");
-    *next_step = s->pos;
-    return BBB_OK;
-}
-
-int bbb_awgn_stream_close(bbb_awgn_stream *s) {
+static int seq_close(SeqStream *s) {
     if (!s) return BBB_OK;
     int rc = BBB_OK;
     if (s->h) {
@@ -1384,6 +1388,37 @@ int bbb_awgn_stream_close(bbb_awgn_stream *s) {
     delete s;
     return rc;
 }
+
+struct bbb_awgn_stream : SeqStream {
+    int elem = 1;
+    int fill(void *dst_dev, uint64_t nsamples) override {
+        return elem == 1 ? bbb_awgn_fill_i8(h, (int8_t *)dst_dev, nsamples, pos) : bbb_awgn_fill_i16(h, (int16_t *)dst_dev, nsamples, pos);
+    }
+    int hint() override { return pos + n >= pos ? bbb_awgn_prefetch(h, n, pos) : BBB_OK; }
+};
+
+int bbb_awgn_stream_open(bbb_lutopt *h, uint64_t nsamples_per_call, uint64_t first_step, int elem_bytes, bbb_awgn_stream **out) {
+    if (!h || !out) return fail(BBB_EINVAL, "null argument");
+    if (nsamples_per_call == 0) return fail(BBB_EINVAL, "nsamples_per_call must be positive");
+    if (elem_bytes != 1 && elem_bytes != 2) return fail(BBB_EINVAL, "elem_bytes must be 1 (int8) or 2 (int16)");
+    if (h->device < 0) return fail(BBB_ENODEV, "host-only handle (device -1) cannot generate samples");
+    if (h->k & (h->k - 1)) return fail(BBB_EUNSUP, "CLTGRNG needs k to be a power of two (rng.py:72-76)");
+    if (elem_bytes == 1 && h->k > 256) return fail(BBB_EUNSUP, "k > 256 needs the int16 output");
+    std::unique_ptr<bbb_awgn_stream> s(new bbb_awgn_stream);
+    s->elem = elem_bytes;
+    // two reads per sample kernel (look-ahead 2): a sequential reader is exactly the consumer that level is for, and it
+    // halves the start-state derivations -- beside the sample kernel the guests (mover, then seeding) otherwise take
+    // about as long as the kernel itself (same box, 1e9 per read: 1.16 ms per read at level 1, 1.055 at 2, 1.09 at 4)
+    const int rc = s->open(h, nsamples_per_call, first_step, "first_step", true);
+    if (!rc) *out = s.release();
+    return rc;
+}
+
+int bbb_awgn_stream_read(bbb_awgn_stream *s, void *dst_dev, uint64_t nsamples) { return seq_read(s, dst_dev, nsamples); }
+int bbb_awgn_stream_next(bbb_awgn_stream *s, void *dst_dev) { return seq_next(s, dst_dev); }
+int bbb_awgn_stream_seek(bbb_awgn_stream *s, uint64_t first_step) { return seq_seek(s, first_step, "first_step"); }
+int bbb_awgn_stream_tell(const bbb_awgn_stream *s, uint64_t *next_step) { return seq_tell(s, next_step); }
+int bbb_awgn_stream_close(bbb_awgn_stream *s) { return seq_close(s); }
 
 int bbb_lutopt_fill_words(bbb_lutopt *h, uint32_t *dst_dev, uint64_t nstates, uint64_t first_step, int msb_first) {
     if (!h) return fail(BBB_EINVAL, "null handle");
@@ -1576,13 +1611,11 @@ int bbb_tx_fill_i16(bbb_lutopt *h, const bbb_tx_cfg *cfg, int16_t *out_dev, uint
             auto make_bits = [&](int slot, uint64_t nbits_all) -> int {
                 words64 = 2 + (nbits_all + 63) / 64 + 3;
                 // the slot's OTHER buffer than last time: its readers were the movers of the slot's kernel before last; the slot's last
-                // kernel waited for them (stage_free stands for every mover of the slot so far) and was queued on this stream
-                bits_buf = h->mbits_turn[slot] ^= 1u;
-                if (h->d_mbits[slot][bits_buf].cap < (size_t)words64 * 2) {
-                    if (h->stage_busy[slot]) BBB_HIP(hipEventSynchronize(h->stage_free[slot]));      // growing frees the old buffer
-                    if (const int rcg = h->d_mbits[slot][bits_buf].grow((size_t)words64 * 2)) return rcg;
-                }
-                d_bits = h->d_mbits[slot][bits_buf];
+                // kernel waited for them (the slot's free event stands for every mover of the slot so far) and was queued on this stream
+                StageSlot &sl = h->slots[slot];
+                bits_buf = sl.bits_turn ^= 1u;
+                if (const int rcg = sl.grow_bits(bits_buf, (size_t)words64 * 2)) return rcg;
+                d_bits = sl.bits[bits_buf];
                 if (!cfg->bit_en || !nbits_all) return BBB_OK;
                 BBB_HIP(hipMemsetAsync(d_bits, 0, 16, h->cs));
                 uint64_t *bits64 = (uint64_t *)d_bits + 2;
@@ -1600,7 +1633,7 @@ int bbb_tx_fill_i16(bbb_lutopt *h, const bbb_tx_cfg *cfg, int16_t *out_dev, uint
             if ((rc = take_waiting(h, 1, first_sample, nsamples, cfg, &waiting, &a))) return rc;
             if (waiting) {
                 // its data bits sit in the slot's buffer, behind those of the windows before it
-                d_bits = h->d_mbits[a.slot][a.bits_buf]; words64 = a.bits_words64;
+                d_bits = h->slots[a.slot].bits[a.bits_buf]; words64 = a.bits_words64;
                 rel = (uint32_t)(FM - 7 - (a.bits_m0 - 128));
                 bits_on = cfg->bit_en != 0;
                 return queue_mover_with(h, a.slot, [&](const void *stage, hipStream_t ys) {
@@ -1678,20 +1711,17 @@ int bbb_tx_fill_i16(bbb_lutopt *h, const bbb_tx_cfg *cfg, int16_t *out_dev, uint
 // The transmitter as a sequential-stream object: TX.x is one sample per clock (tx.py:39-81), and a host that reads it in equal
 // calls should get the staged form without choreographing bbb_lutopt_set_staged / bbb_awgn_prefetch itself (the
 // counterpart of bbb_awgn_stream_* for the waveform).
-struct bbb_tx_stream {
-    bbb_lutopt *h = nullptr;
+struct bbb_tx_stream : SeqStream {
     bbb_tx_cfg cfg{};
-    uint64_t n = 0, pos = 0;
-    int saved_level = 0;
+    int fill(void *dst_dev, uint64_t nsamples) override { return bbb_tx_fill_i16(h, &cfg, (int16_t *)dst_dev, nsamples, pos); }
+    int hint() override {
+        // the noise of sample p is LUTOPT clock warmup + p (tx.py:70-71): what bbb_tx_fill_i16 will ask the generator for
+        if (!cfg.noise_en) return BBB_OK;
+        const uint64_t step = cfg.warmup + pos;
+        if (step < pos || step + n < step) return BBB_OK;
+        return awgn_prefetch(h, n, step, true);
+    }
 };
-
-static int tx_stream_hint(bbb_tx_stream *s) {
-    // the noise of sample p is LUTOPT clock warmup + p (tx.py:70-71): what bbb_tx_fill_i16 will ask the generator for
-    if (!s->cfg.noise_en) return BBB_OK;
-    const uint64_t step = s->cfg.warmup + s->pos;
-    if (step < s->pos || step + s->n < step) return BBB_OK;
-    return awgn_prefetch(s->h, s->n, step, true);
-}
 
 int bbb_tx_stream_open(bbb_lutopt *h, const bbb_tx_cfg *cfg, uint64_t nsamples_per_call, uint64_t first_sample, bbb_tx_stream **out) {
     if (!h || !out) return fail(BBB_EINVAL, "null argument");
@@ -1699,60 +1729,20 @@ int bbb_tx_stream_open(bbb_lutopt *h, const bbb_tx_cfg *cfg, uint64_t nsamples_p
     if (rc) return rc;
     if (nsamples_per_call == 0) return fail(BBB_EINVAL, "nsamples_per_call must be positive");
     if (h->device < 0) return fail(BBB_ENODEV, "host-only handle (device -1) cannot generate samples");
-    if (h->has_stream) return fail(BBB_EINVAL, "the handle already has an open stream");
-    if (first_sample + nsamples_per_call < first_sample) return fail(BBB_EINVAL, "first_sample + nsamples_per_call overflows");
     std::unique_ptr<bbb_tx_stream> s(new bbb_tx_stream);
-    s->h = h; s->cfg = *cfg; s->n = nsamples_per_call; s->pos = first_sample;
-    s->saved_level = h->staged_level;
-    if (h->staged_level == 0 && cfg->noise_en) {      // (a caller who chose a level keeps it)
-        // one noise kernel per two calls: per noise kernel the guests (a shaping mover per call, then the next kernel's
-        // seeding) run one at a time and must fit into its time (1e9 samples per call: 1.44 ms at level 1, 1.28 at 2)
-        if ((rc = bbb_lutopt_set_staged(h, 2))) return rc;
-    }
-    if ((rc = tx_stream_hint(s.get()))) return rc;
-    h->has_stream = true;
-    *out = s.release();
-    return BBB_OK;
-}
-
-int bbb_tx_stream_read(bbb_tx_stream *s, int16_t *out_dev, uint64_t nsamples) {
-    if (!s || !s->h) return fail(BBB_EINVAL, "null stream");
-    if (s->pos + nsamples < s->pos) return fail(BBB_EINVAL, "the stream position overflows");
-    int rc = bbb_tx_fill_i16(s->h, &s->cfg, out_dev, nsamples, s->pos);
-    if (rc) return rc;
-    s->pos += nsamples;
-    return tx_stream_hint(s);
-}
-
-int bbb_tx_stream_next(bbb_tx_stream *s, int16_t *out_dev) {
-    if (!s) return fail(BBB_EINVAL, "null stream");
-    return bbb_tx_stream_read(s, out_dev, s->n);
-}
-
-int bbb_tx_stream_seek(bbb_tx_stream *s, uint64_t first_sample) {
-    if (!s || !s->h) return fail(BBB_EINVAL, "null stream");
-    if (first_sample + s->n < first_sample) return fail(BBB_EINVAL, "first_sample + nsamples_per_call overflows");
-    s->pos = first_sample;
-    s->h->ahead.valid = false;            // what a noise kernel produced ahead at the old position is dropped
-    return tx_stream_hint(s);
-}
-
-int bbb_tx_stream_tell(const bbb_tx_stream *s, uint64_t *next_sample) {
-    if (!s || !next_sample) return fail(BBB_EINVAL, "null argument");
-    *next_sample = s->pos;
-    return BBB_OK;
-}
-
-int bbb_tx_stream_close(bbb_tx_stream *s) {
-    if (!s) return BBB_OK;
-    int rc = BBB_OK;
-    if (s->h) {
-        s->h->has_stream = false;
-        if (s->h->staged_level != s->saved_level) rc = bbb_lutopt_set_staged(s->h, s->saved_level);
-    }
-    delete s;
+    s->cfg = *cfg;
+    // with noise, one noise kernel per two calls: per noise kernel the guests (a shaping mover per call, then the next kernel's
+    // seeding) run one at a time and must fit into its time (1e9 samples per call: 1.44 ms at level 1, 1.28 at 2)
+    rc = s->open(h, nsamples_per_call, first_sample, "first_sample", cfg->noise_en != 0);
+    if (!rc) *out = s.release();
     return rc;
 }
+
+int bbb_tx_stream_read(bbb_tx_stream *s, int16_t *out_dev, uint64_t nsamples) { return seq_read(s, out_dev, nsamples); }
+int bbb_tx_stream_next(bbb_tx_stream *s, int16_t *out_dev) { return seq_next(s, out_dev); }
+int bbb_tx_stream_seek(bbb_tx_stream *s, uint64_t first_sample) { return seq_seek(s, first_sample, "first_sample"); }
+int bbb_tx_stream_tell(const bbb_tx_stream *s, uint64_t *next_sample) { return seq_tell(s, next_sample); }
+int bbb_tx_stream_close(bbb_tx_stream *s) { return seq_close(s); }
 
 int bbb_rx_slice(const int16_t *samples_dev, uint64_t nsamples, uint64_t stride, uint64_t phase, int strict,
                  uint64_t *bits_packed_dev, uint64_t *nbits_out, int device, void *hip_stream) {

@@ -154,6 +154,22 @@ void tag(const void *p, const std::string &t) {
     if (Buffer *b = buffer_of(p)) b->tag = t;
 }
 
+// A launch that FAILS (leak_check.cpp: what the scheduler holds when it returns early must still find its owner): the nth
+// launch stub entered from now on queues nothing and returns BBB_EHIP, once.
+static int g_refuse_in = 0;                     // launches up to and including the refused one; 0: none
+void fail_nth_launch(int nth) {
+    std::lock_guard<std::mutex> g(g_mu);
+    g_refuse_in = nth;
+}
+bool launch_failure_pending() {
+    std::lock_guard<std::mutex> g(g_mu);
+    return g_refuse_in != 0;
+}
+static bool refused() {
+    std::lock_guard<std::mutex> g(g_mu);
+    return g_refuse_in && --g_refuse_in == 0;
+}
+
 }  // namespace model
 
 using namespace model;
@@ -332,50 +348,61 @@ int prbs_state_at_host(int k, uint64_t init_state, uint64_t nbits, uint64_t *sta
 
 int awgn_seed_launch(int, const uint32_t *d_tabs, const uint32_t *, uint64_t G, uint32_t *d_states, uint64_t, unsigned nlanes, uint32_t *d_planes,
                      hipStream_t st, int slice_mode, int variant) {
+    if (refused()) return BBB_EHIP;
     op(st, "seeding (levels + bitslice)" + args(G, nlanes, slice_mode, variant), {d_tabs, d_states}, {d_states});
     op(st, "bitslice", {d_states}, {d_planes});
     return BBB_OK;
 }
 int awgn_seed_head_launch(int, const uint32_t *d_tabs, const uint32_t *, uint64_t G, uint32_t *d_states, hipStream_t st, const PrbsSeedRide *ride) {
+    if (refused()) return BBB_EHIP;
     if (ride) op(st, "seed_head_kernel (+ PRBS lanes)" + args(G), {d_tabs, ride->d_tabs}, {d_states, ride->d_planes});
     else op(st, "seed_head_kernel" + args(G), {d_tabs}, {d_states});
     return BBB_OK;
 }
 int awgn_seed_tail_planes_launch(int, const uint32_t *d_top, uint64_t G, const uint32_t *d_states, unsigned nlanes, uint32_t *d_planes, hipStream_t st) {
+    if (refused()) return BBB_EHIP;
     op(st, "seed_tail_planes_kernel" + args(G, nlanes), {d_top, d_states}, {d_planes});
     return BBB_OK;
 }
 int prbs_seed_planes_launch(int, const uint32_t *d_tabs, const uint32_t *, uint64_t, uint32_t *d_states, unsigned, uint32_t *d_planes, hipStream_t st) {
+    if (refused()) return BBB_EHIP;
     op(st, "PRBS seeding", {d_tabs}, {d_states});
     op(st, "PRBS bitslice", {d_states}, {d_planes});
     return BBB_OK;
 }
 int prbs_seed_lanes_launch(int, const uint32_t *d_tabs, const uint32_t *, const uint32_t *, uint64_t, unsigned, uint32_t *d_planes, hipStream_t st) {
+    if (refused()) return BBB_EHIP;
     op(st, "PRBS seeding (one state per lane + Q steps)", {d_tabs}, {d_planes});
     return BBB_OK;
 }
 int awgn512p_fill_launch(const uint32_t *d_planes, int16_t *dst, uint64_t, unsigned, uint64_t, unsigned, hipStream_t st) {
+    if (refused()) return BBB_EHIP;
     op(st, "awgn512p kernel", {d_planes}, {dst});
     return BBB_OK;
 }
 int bitslice512p_launch(const uint32_t *d_states, uint64_t, uint64_t, unsigned, uint32_t *d_planes, hipStream_t st) {
+    if (refused()) return BBB_EHIP;
     op(st, "bitslice512p", {d_states}, {d_planes});
     return BBB_OK;
 }
 int awgn256_fill_launch(const uint32_t *d_planes, int8_t *dst, uint64_t, unsigned, uint64_t, unsigned, hipStream_t st) {
+    if (refused()) return BBB_EHIP;
     op(st, "awgn256_kernel (one-kernel form)", {d_planes}, {dst});
     return BBB_OK;
 }
 int awgn256_planes_launch(const uint32_t *d_planes, void *stage, unsigned L, unsigned nlanes, hipStream_t st, bool small) {
+    if (refused()) return BBB_EHIP;
     op(st, (small ? "awgn256_planes_kernel<small>" : "awgn256_planes_kernel") + args(L, nlanes, small), {d_planes}, {stage});
     return BBB_OK;
 }
 int unplane_launch(const void *stage, void *dst, uint64_t win_lo, uint64_t nbytes, unsigned L, uint64_t G, unsigned nlanes, hipStream_t st) {
+    if (refused()) return BBB_EHIP;
     op(st, "unplane_kernel (mover) window [" + std::to_string(win_lo) + ", +" + std::to_string(nbytes) + ")" + args(L, G, nlanes), {stage}, {dst});
     return BBB_OK;
 }
 int unplane_tx_launch(const void *stage, int16_t *dst, uint64_t win_lo, uint64_t nsamples, unsigned L, uint64_t G, unsigned nlanes, const int16_t *,
                       const uint32_t *d_bits, uint32_t nwords32, uint32_t rel_base, uint32_t c0, int noise_var, int bit_en, int use_bits, hipStream_t st) {
+    if (refused()) return BBB_EHIP;
     const std::string what = "unplane_kernel<TX> (shaping mover)" + args(win_lo, nsamples, L, G, nlanes, nwords32, rel_base, c0, noise_var, bit_en, use_bits);
     if (use_bits) op(st, what, {stage, d_bits}, {dst});
     else op(st, what, {stage}, {dst});
@@ -383,76 +410,92 @@ int unplane_tx_launch(const void *stage, int16_t *dst, uint64_t win_lo, uint64_t
 }
 int awgn256_tx_launch(const uint32_t *d_planes, int16_t *dst, uint64_t, unsigned, uint64_t, unsigned, const int16_t *, const uint32_t *d_bits,
                       uint32_t, uint32_t, uint32_t, int, int, int use_bits, hipStream_t st) {
+    if (refused()) return BBB_EHIP;
     if (use_bits) op(st, "awgn256_kernel<TX>", {d_planes, d_bits}, {dst});
     else op(st, "awgn256_kernel<TX>", {d_planes}, {dst});
     return BBB_OK;
 }
 int pulse_bits_launch(uint64_t *dst, int64_t m_first, uint64_t nwords, hipStream_t st) {
+    if (refused()) return BBB_EHIP;
     if (nwords) op(st, "pulse_bits_kernel" + args(m_first, nwords), {}, {dst});
     return BBB_OK;
 }
 int widen_i8_i16_launch(const int8_t *src, int16_t *dst, uint64_t, hipStream_t st) {
+    if (refused()) return BBB_EHIP;
     op(st, "widen_i8_i16_kernel", {src}, {dst});
     return BBB_OK;
 }
 int awgn_generic_fill_launch(int, const uint16_t *d_taps, const uint32_t *d_row_off, uint32_t *d_planes2, void *dst, int, uint64_t, unsigned,
                              uint64_t, unsigned, hipStream_t st) {
+    if (refused()) return BBB_EHIP;
     op(st, "awgn_generic_kernel", {d_taps, d_row_off, d_planes2}, {d_planes2, dst});
     return BBB_OK;
 }
 int lutopt_words_launch(int, const uint16_t *d_taps, const uint32_t *d_row_off, uint32_t *d_planes2, uint32_t *dst, uint64_t, unsigned, uint64_t,
                         unsigned, bool, hipStream_t st) {
+    if (refused()) return BBB_EHIP;
     op(st, "lutopt_words_kernel", {d_taps, d_row_off, d_planes2}, {d_planes2, dst});
     return BBB_OK;
 }
 int lutopt_words256_launch(const uint32_t *d_planes, uint32_t *dst, uint64_t, unsigned, uint64_t, unsigned, bool, hipStream_t st) {
+    if (refused()) return BBB_EHIP;
     op(st, "lutopt_words256_kernel", {d_planes}, {dst});
     return BBB_OK;
 }
 int clt_tree_launch(int, const uint64_t *states, uint64_t, int16_t *out, hipStream_t st) {
+    if (refused()) return BBB_EHIP;
     op(st, "clt_tree_kernel", {states}, {out});
     return BBB_OK;
 }
 int awgn_small_fill_launch(int, const uint32_t *d_planes, int8_t *dst, uint64_t, unsigned, uint64_t, unsigned, hipStream_t st) {
+    if (refused()) return BBB_EHIP;
     op(st, "awgn_small_kernel", {d_planes}, {dst});
     return BBB_OK;
 }
 int ber256_launch(uint32_t *d_planes, uint32_t *d_prbs_planes, const TrialDev *t, int, unsigned, unsigned long long *d_counters, hipStream_t st) {
+    if (refused()) return BBB_EHIP;
     if (t[0].flags & kTrialSaveState) op(st, "ber256_fused_kernel (continued: leaves its states)", {d_planes, d_prbs_planes, d_counters}, {d_planes, d_prbs_planes, d_counters});
     else op(st, "ber256_fused_kernel", {d_planes, d_prbs_planes, d_counters}, {d_counters});
     return BBB_OK;
 }
 int tx_waveform_launch(const int16_t *, const uint64_t *d_bits, int64_t, uint64_t, int source, const int8_t *d_noise, int, int, int noise_en,
                        uint64_t, uint64_t, int16_t *d_out, hipStream_t st) {
+    if (refused()) return BBB_EHIP;
     (void)source;
     if (noise_en && d_noise) op(st, "tx_waveform_kernel", {d_bits, d_noise}, {d_out});
     else op(st, "tx_waveform_kernel", {d_bits}, {d_out});
     return BBB_OK;
 }
 int rx_slice_launch(const int16_t *d_samples, uint64_t, uint64_t, uint64_t, int, uint64_t *d_out, hipStream_t st) {
+    if (refused()) return BBB_EHIP;
     op(st, "rx_slice_kernel", {d_samples}, {d_out});
     return BBB_OK;
 }
 int prbs_fill_launch(int, uint64_t, uint64_t first_bit, uint64_t nbits, uint64_t *dst, hipStream_t st, int) {
+    if (refused()) return BBB_EHIP;
     if (nbits) op(st, "prbs_stream_kernel (fill)" + args(first_bit, nbits), {}, {dst});
     return BBB_OK;
 }
 int prbs_check_launch(int, uint64_t, uint64_t, uint64_t nbits, const uint64_t *src, uint64_t *nerr_dev, hipStream_t st) {
+    if (refused()) return BBB_EHIP;
     if (nbits) op(st, "prbs_check_rev_kernel", {src, nerr_dev}, {nerr_dev});
     return BBB_OK;
 }
 int prbs_detector_launch(int, const uint8_t *bits, uint64_t, uint64_t, uint8_t *err, uint8_t *reload, hipStream_t st) {
+    if (refused()) return BBB_EHIP;
     op(st, "prbs_detector_kernel", {bits}, {err, reload});
     return BBB_OK;
 }
 int prbs_detector_stream_launch(int, const uint64_t *src, uint64_t, uint64_t *err, uint64_t *reload, bbb_detector_stats *stats, uint64_t, uint64_t,
                                 hipStream_t st) {
+    if (refused()) return BBB_EHIP;
     op(st, "detector stream (chunk pass ... read-back)", {src}, {err, reload});
     if (stats) *stats = bbb_detector_stats{};
     hipStreamSynchronize(st);
     return BBB_OK;
 }
 int lutopt_search_launch(int, uint64_t, uint64_t, uint64_t, uint64_t *found, uint16_t *, uint32_t *, bbb_search_stats *stats, hipStream_t st) {
+    if (refused()) return BBB_EHIP;
     if (found) *found = ~0ull;
     if (stats) *stats = bbb_search_stats{};
     hipStreamSynchronize(st);

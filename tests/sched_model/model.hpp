@@ -27,6 +27,8 @@ const std::vector<std::string> &errors();
 void clear_errors();
 uint64_t ops_checked();
 uint64_t transcript();                            // the running hash over everything logged so far (model.cpp)
+void fail_nth_launch(int nth);                    // the nth kernel-launch stub from now on returns BBB_EHIP, once (0: none does)
+bool launch_failure_pending();                    // ... and has not done so yet
 
 // " (a, b, ...)": a launch stub's scalar arguments, appended to its operation text so that the transcript covers them
 template <typename... T>

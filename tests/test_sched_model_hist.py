@@ -22,8 +22,8 @@ MODEL = ROOT / "tests" / "sched_model"
 TAPS = str(ROOT / "basebandboard_amd" / "data" / "lutopt_256.taps")
 
 MUTANTS = {
-    "mover_chain": [("""    if (h->stage_busy[slot]) BBB_HIP(hipStreamWaitEvent(ms, h->stage_free[slot], 0));
-    hipEvent_t m0 = nullptr, m1 = nullptr;""", """    hipEvent_t m0 = nullptr, m1 = nullptr;""")],
+    "mover_chain": [("""    if ((rc = sl.wait_free(ms))) return rc;
+""", "")],
     "visit_independent": [("int rc = begin_op(h, true, h->pf.matches(seed_step, L, G));", "int rc = begin_op(h, true, true);")],
 }
 
