@@ -27,6 +27,7 @@ SYMBOLS = [
     "bbb_errstat_set_stream", "bbb_errstat_geometry", "bbb_errstat_close",
     "bbb_xcorr_accumulate_i16", "bbb_tx_xcorr_open", "bbb_tx_xcorr_run", "bbb_tx_xcorr_close",
     "bbb_ddc_run", "bbb_ddc_polar_host",
+    "bbb_dfe_run", "bbb_dfe_geometry", "bbb_dfe_model_host",
 ]
 
 
@@ -101,6 +102,12 @@ class FirCfg(C.Structure):
 
 
 DDC_IQ16, DDC_IQ32, DDC_POLAR = 0, 1, 2
+
+
+class DfeCfg(C.Structure):
+    """bbb_dfe_cfg"""
+    _fields_ = [("ff", FirCfg), ("nfb", C.c_uint32), ("fb", C.c_int32 * 4), ("threshold", C.c_int32), ("strict", C.c_uint32),
+                ("region_symbols", C.c_uint32), ("warmup_symbols", C.c_uint32)]
 
 
 class DdcCfg(C.Structure):
@@ -263,6 +270,9 @@ def lib():
     l.bbb_tx_xcorr_close.argtypes = [vp]
     l.bbb_ddc_run.argtypes = [vp, u64, C.c_uint32, u64, C.POINTER(DdcCfg), C.POINTER(FirCfg), vp, u64p, i32, vp]
     l.bbb_ddc_polar_host.argtypes = [C.c_int16, C.c_int16, C.POINTER(C.c_uint16), C.POINTER(C.c_int16)]
+    l.bbb_dfe_run.argtypes = [vp, u64, C.c_uint32, C.POINTER(DfeCfg), vp, vp, vp, vp, u64p, i32, vp]
+    l.bbb_dfe_geometry.argtypes = [C.c_uint32, u64p, u64p, u64p, u64p, u64p]
+    l.bbb_dfe_model_host.argtypes = [vp, u64, C.c_uint32, C.POINTER(DfeCfg), C.POINTER(C.c_uint32), vp, vp, u64p]
     u8p = C.POINTER(C.c_uint8)
     l.bbb_gf2_berlekamp_massey.argtypes = [u8p, u64, u8p, C.POINTER(C.c_int64)]
     l.bbb_gf2_recur.argtypes = [i32, i32, u64p, u8p, i32, u8p]

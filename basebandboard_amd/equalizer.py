@@ -117,15 +117,16 @@ def noise_power(acf0, count, h, spb):
     return max(0.0, float(acf0) / float(count) - float((h * h).sum()) / int(spb))
 
 
-def _mmse_system(h, spb, cursor, ntaps, noise_power):
+def _mmse_system(h, spb, cursor, ntaps, noise_power, nfb=0):
     h = np.asarray(h, dtype=np.float64)
     L, spb, cursor, ntaps = len(h), int(spb), int(cursor), int(ntaps)
     # G[i, k] = h[cursor - i + spb * k] over every bit offset k at which some tap sees the pulse (0 outside its lags)
     k = np.arange(-((cursor + spb - 1) // spb) - 1, (L + ntaps) // spb + 2, dtype=np.int64)
     idx = cursor - np.arange(ntaps, dtype=np.int64)[:, None] + spb * k[None, :]
     G = np.where((idx >= 0) & (idx < L), h[np.clip(idx, 0, L - 1)], 0.0)
-    R = G @ G.T + float(noise_power) * np.eye(ntaps)
     p = G[:, int(np.flatnonzero(k == 0)[0])]
+    G = G[:, (k < 1) | (k > int(nfb))]           # the nfb bits in front of the cursor's are the feedback's to remove
+    R = G @ G.T + float(noise_power) * np.eye(ntaps)
     return R, p
 
 
@@ -144,6 +145,10 @@ def mmse_taps(h, spb, cursor, ntaps, noise_power, scale_bits=8):
     filtered bathtub's best phase is the unfiltered one's.  FIR.delay() is the centroid of |taps| instead; for a filter whose
     largest tap answers the peak (tap cursor - peak) the two agree to within the taps' asymmetry, and the centroid is what
     remains when no pulse response is known."""
+    return _mmse_design(h, spb, cursor, ntaps, noise_power, scale_bits, 0)
+
+
+def _mmse_design(h, spb, cursor, ntaps, noise_power, scale_bits, nfb):
     h = np.asarray(h, dtype=np.float64)
     spb, cursor, ntaps = int(spb), int(cursor), int(ntaps)
     if h.ndim != 1 or len(h) == 0 or not np.abs(h).max() > 0:
@@ -155,7 +160,7 @@ def mmse_taps(h, spb, cursor, ntaps, noise_power, scale_bits=8):
     peak = int(np.abs(h).argmax())
     if not peak <= cursor < len(h) + ntaps - 1:
         raise ValueError(f"cursor must be {peak} (the pulse's peak) .. {len(h) + ntaps - 2}")
-    R, p = _mmse_system(h, spb, cursor, ntaps, noise_power)
+    R, p = _mmse_system(h, spb, cursor, ntaps, noise_power, nfb)
     try:
         w = np.linalg.solve(R, p)
     except np.linalg.LinAlgError:
@@ -166,6 +171,26 @@ def mmse_taps(h, spb, cursor, ntaps, noise_power, scale_bits=8):
         raise ValueError("no tap sees the pulse: move the cursor or lengthen the filter")
     taps = np.clip(np.rint(w * (1 << int(scale_bits)) / np.abs(w).max()), -32768, 32767).astype(np.int16)
     return taps, cursor - peak
+
+
+def dfe_taps(h, spb, cursor, nff, nfb, noise_power, scale_bits=8):
+    """The MMSE decision-feedback design for white +-1 data: (ff, fb, delay) for dfe.DFE.
+
+    The feed-forward filter is mmse_taps' system R w = p with the nfb bits in front of the cursor's taken out of the
+    interference (bit m - k reaches tap i through h[cursor - i + spb k]; k = 1 .. nfb are decided already and the feedback
+    removes them), scaled to int16 taps the same way.  The feedback taps are what the INTEGER feed-forward filter makes of
+    those bits, fb[i] = round(sum_j ff[j] h[cursor - j + spb (i + 1)]), so they are in units of the filter's acc and undo
+    exactly what the filter that runs lets through.  fb is an int64 numpy array of nfb entries; nfb = 0 gives mmse_taps'
+    taps.  delay as in mmse_taps."""
+    nfb = int(nfb)
+    if not 0 <= nfb <= 4:
+        raise ValueError("nfb must be 0..4")
+    ff, delay = _mmse_design(h, spb, cursor, nff, noise_power, scale_bits, nfb)
+    h = np.asarray(h, dtype=np.float64)
+    idx = int(cursor) - np.arange(len(ff), dtype=np.int64)[None, :] + int(spb) * np.arange(1, nfb + 1, dtype=np.int64)[:, None]
+    post = np.where((idx >= 0) & (idx < len(h)), h[np.clip(idx, 0, len(h) - 1)], 0.0)
+    fb = np.rint(post @ ff.astype(np.float64)).astype(np.int64)
+    return ff, fb, delay
 
 
 def tx_pulse_response(tx, nsamples, nlags=64, first_sample=0, warmup=16, chunk_samples=0):

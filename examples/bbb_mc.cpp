@@ -29,6 +29,9 @@
 //                       (bbb_fir_slice with the taps of bbb_fir_moving_average) beside the plain sign slicer (bbb_rx_slice) over a
 //                       noisy transmission of the 4-sample rectangular pulse (the last set of PRBSShaper.from_rcf), each at 8
 //                       samples per bit into the exact detector: one JSON line with both error counts
+//          dfe:         --dfe 1 [--eye-samples 1e6] [--prbs 31] [--nv 8]   the same receiver behind an echo of 0.7 one bit late
+//                       (bbb_fir_filter as the channel), without and with one feedback tap (bbb_dfe_run): errors of both
+//                       from the exact detector, and the call's region counters
 //          link:        --link 1 [--eye-samples 1e6] [--prbs 31] [--nv 8] [--shape 16] [--delay 2]   the bathtub of one transmitter
 //                       setting decided on the raw sample (bbb_tx_ber_sweep_*) and behind the moving average of rx.py:24-26
 //                       (bbb_link_sweep_* with the taps of bbb_fir_moving_average, the filtered stream re-timed by `delay`), the
@@ -203,7 +206,7 @@ int main(int argc, char **argv) {
     bool lags_set = false;
     int shape = 16, eye_shift = 4;
     double eye_samples = 1e6;
-    int tx_sweep = 0, nv_lo = 0, nv_hi = 15, fir = 0, link = 0, link_delay = 2, errstat = 0, xcorr = 0, ddc = 0, nco_pm = 100;
+    int tx_sweep = 0, nv_lo = 0, nv_hi = 15, fir = 0, dfe = 0, link = 0, link_delay = 2, errstat = 0, xcorr = 0, ddc = 0, nco_pm = 100;
     unsigned long errstat_guard = 64;
     unsigned long long init0 = 1;
     double bits = 1e9, from = 0, to = 10, step = 1, loopback = 0, nsamples = 0, grng_eval = 0;
@@ -250,6 +253,7 @@ int main(int argc, char **argv) {
         else if (a == "--shift") eye_shift = std::atoi(v);
         else if (a == "--tx-sweep") tx_sweep = std::atoi(v);
         else if (a == "--fir") fir = std::atoi(v);
+        else if (a == "--dfe") dfe = std::atoi(v);
         else if (a == "--link") link = std::atoi(v);
         else if (a == "--delay") link_delay = std::atoi(v);
         else if (a == "--errstat") errstat = std::atoi(v);
@@ -695,6 +699,69 @@ int main(int argc, char **argv) {
                     "\"seconds\": %.4f}\n", (unsigned long long)ntx, k, nv, (unsigned long long)plain.bits, (unsigned long long)plain.errors,
                     (unsigned long long)plain.reload_clocks, (unsigned long long)filt.bits, (unsigned long long)filt.errors,
                     (unsigned long long)filt.reload_clocks, secs);
+        return 0;
+    }
+
+    // ---- an echo one bit late: the moving-average receiver beside the same filter with one feedback tap (bbb_dfe_run) ---------
+    if (dfe) {
+        if (eye_samples < 1 || nv < 0 || nv > 15) { std::fprintf(stderr, "--eye-samples >= 1, --nv 0..15\n"); return 2; }
+        bbb_tx_cfg cfg{};
+        for (int i = 30; i < 34; i++) cfg.coeffs[i] = 254;          // the rectangular pulse (bitshaper.py:108)
+        cfg.source = 0;
+        cfg.prbs_k = k;
+        cfg.prbs_state = 1;
+        cfg.bit_en = 1;
+        cfg.noise_en = 1;
+        cfg.noise_var = nv;
+        cfg.warmup = 16;
+        const uint64_t init[8] = {init0, 0, 0, 0, 0, 0, 0, 0};
+        bbb_lutopt *h = nullptr;
+        CHECK(bbb_lutopt_create(&h, m.n, m.taps.data(), m.off.data(), init, 0));
+        const uint64_t ntx = (uint64_t)eye_samples;
+        int16_t *w = nullptr, *y = nullptr;
+        uint64_t *b = nullptr, *stats = nullptr;
+        uint32_t *state = nullptr;
+        if (hipMalloc((void **)&w, ntx * sizeof(int16_t)) != hipSuccess || hipMalloc((void **)&y, ntx * sizeof(int16_t)) != hipSuccess ||
+            hipMalloc((void **)&b, (ntx / 8 / 64 + 2) * sizeof(uint64_t)) != hipSuccess || hipMalloc((void **)&stats, 4 * sizeof(uint64_t)) != hipSuccess ||
+            hipMalloc((void **)&state, sizeof(uint32_t)) != hipSuccess || hipMemset(stats, 0, 4 * sizeof(uint64_t)) != hipSuccess ||
+            hipMemset(state, 0, sizeof(uint32_t)) != hipSuccess) {
+            std::fprintf(stderr, "hipMalloc failed\n");
+            return 1;
+        }
+        CHECK(bbb_tx_fill_i16(h, &cfg, w, ntx, 0));
+        // the channel: y(n) = (10 x(n) + 7 x(n - 8)) >> 4, an echo of 0.7 one bit late
+        bbb_fir_cfg ch{};
+        ch.ntaps = 9, ch.taps[0] = 10, ch.taps[8] = 7, ch.shift = 4, ch.decim = 1, ch.out_bytes = 2;
+        CHECK(bbb_fir_filter(w, ntx, 0, &ch, y, nullptr, 0, nullptr));
+        // bit m holds samples 8m + 47 .. 8m + 50 at 254 * 10 >> 4 = 158 and its echo at 254 * 7 >> 4 = 111: the running sum of
+        // four is complete at 8m + 50 and carries 4 * 111 of the bit before
+        uint64_t nlin = 0, ndfe = 0;
+        bbb_detector_stats lin{}, eq{};
+        const double t0 = now_s();
+        bbb_dfe_cfg dc{};
+        CHECK(bbb_fir_moving_average(&dc.ff, 0));
+        dc.ff.decim = 8;
+        dc.ff.phase = 2;
+        CHECK(bbb_fir_slice(y, ntx, 0, &dc.ff, 0, 0, b, &nlin, 0, nullptr));
+        CHECK(bbb_prbs_detector_stream(k, b, nlin, nullptr, nullptr, &lin, 0, 0, 0, nullptr));
+        dc.nfb = 1;
+        dc.fb[0] = 4 * 111;
+        CHECK(bbb_dfe_run(y, ntx, 0, &dc, state, b, nullptr, stats, &ndfe, 0, nullptr));
+        CHECK(bbb_prbs_detector_stream(k, b, ndfe, nullptr, nullptr, &eq, 0, 0, 0, nullptr));
+        const double secs = now_s() - t0;
+        uint64_t st[4] = {0, 0, 0, 0};
+        if (hipMemcpy(st, stats, sizeof st, hipMemcpyDeviceToHost) != hipSuccess) { std::fprintf(stderr, "copy failed\n"); return 1; }
+        CHECK(bbb_lutopt_destroy(h));
+        (void)hipFree(w);
+        (void)hipFree(y);
+        (void)hipFree(b);
+        (void)hipFree(stats);
+        (void)hipFree(state);
+        std::printf("{\"mode\": \"dfe\", \"samples\": %llu, \"prbs\": %d, \"nv\": %d, \"echo\": 0.7, \"moving_average\": {\"bits\": %llu, \"errors\": %llu}, "
+                    "\"dfe\": {\"fb\": %d, \"bits\": %llu, \"errors\": %llu, \"regions\": %llu, \"not_proven\": %llu, \"repaired\": %llu}, "
+                    "\"seconds\": %.4f}\n", (unsigned long long)ntx, k, nv, (unsigned long long)lin.bits, (unsigned long long)lin.errors, dc.fb[0],
+                    (unsigned long long)eq.bits, (unsigned long long)eq.errors, (unsigned long long)st[0], (unsigned long long)st[1],
+                    (unsigned long long)st[2], secs);
         return 0;
     }
 

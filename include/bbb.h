@@ -718,6 +718,55 @@ int bbb_ddc_run(const int16_t *in_dev, uint64_t nin, uint32_t nbefore, uint64_t 
 /* The CORDIC of BBB_DDC_POLAR for one pair (host only, works without a GPU). */
 int bbb_ddc_polar_host(int16_t i, int16_t q, uint16_t *mag, int16_t *phase);
 
+/* ---- decision-feedback equalizer: feed-forward FIR, up to 4 feedback taps, exact whatever the data are ------------------- */
+
+/* The receiver's step behind the linear equalizer: the post-cursor interference of the bits already decided is subtracted
+ * before the next decision.  With ff a bbb_fir_cfg under its own rules (decim = samples per bit, phase = sampling phase,
+ * acc(n) exact in int32, history by nbefore) and nsym = nout of ff, for symbol k in [0, nsym):
+ *   a[k]   = acc(phase + k * decim)
+ *   v[k]   = a[k] - sum_{i = 1..nfb} fb[i - 1] * d[k - i]        d[j] = +1 if bit[j] else -1
+ *   bit[k] = v[k] >= threshold      (> threshold with strict != 0)
+ * nfb is 0..BBB_DFE_MAX_FB, fb[] in units of acc; 32768 * sum |ff.taps| + sum |fb| <= 2^31 - 1 keeps v exact in int32 in any
+ * order (BBB_EINVAL otherwise).  The decisions in front of symbol 0 are the state word: bit i is the decision of symbol
+ * k - 1 - i; bits from nfb on are ignored on input and written as 0; a zeroed word is the shift register out of reset
+ * (earlier bits count as 0, the shaper's convention).  nfb = 0 is bbb_fir_slice bit for bit.
+ * region_symbols / warmup_symbols (0: the defaults of bbb_dfe_geometry) only place the boundaries of the work on the device:
+ * no output depends on them. */
+#define BBB_DFE_MAX_FB 4
+typedef struct {
+    bbb_fir_cfg ff;          /* shift and out_bytes count only where soft values are asked for */
+    uint32_t nfb;            /* 0..4 */
+    int32_t  fb[4];          /* fb[i] weighs the decision i + 1 symbols back */
+    int32_t  threshold;
+    uint32_t strict;
+    uint32_t region_symbols; /* symbols one workgroup owns; 0: the default */
+    uint32_t warmup_symbols; /* symbols run in front of a region to find its start state; 0: the default */
+} bbb_dfe_cfg;
+
+/* bits_packed_dev: bit[k] LSB first in u64 words, the layout of bbb_fir_slice, the unused bits of the last word 0
+ * (ceil(nsym / 64) words, 8-byte aligned).  soft_dev (may be NULL): nsym values, sat16(v[k] >> ff.shift) as int16 with
+ * ff.out_bytes 2, v[k] itself as int32 with ff.out_bytes 4 -- the equalized eye that bbb_eye_accumulate_i16 and the
+ * histogram read.  state_dev: ONE uint32 on the device, read at the start and written at the end, so a record handed over in
+ * pieces (each with its nbefore samples and this word) never synchronises and gives the bits, soft values and final state
+ * of one call.  stats_dev (may be NULL): uint64[4] on the device, ADDED TO: regions, regions whose start state was not proven
+ * by their warm-up, regions walked a second time, symbols.  *nbits_out (host, may be NULL) receives nsym.  in_dev as in
+ * bbb_fir_filter.  BBB_EINVAL before the device is touched: everything wrong with cfg, nulls, misaligned pointers, outputs
+ * that overlap the samples read or each other, more than 2^26 regions.  nin = 0 only rewrites the state word (masked to nfb
+ * bits).  The call's scratch (24 bytes per region) comes from the device's memory pool on hip_stream.  Asynchronous. */
+int bbb_dfe_run(const int16_t *in_dev, uint64_t nin, uint32_t nbefore, const bbb_dfe_cfg *cfg, uint32_t *state_dev,
+                uint64_t *bits_packed_dev, void *soft_dev, uint64_t *stats_dev, uint64_t *nbits_out, int device,
+                void *hip_stream);
+/* Where the device cuts the work (host only, works without a GPU; every pointer may be NULL): a workgroup stages
+ * *step_samples inputs at a time, which hold at most *step_symbols symbols at this decim (symbol k lies in step
+ * (phase + k * decim) / *step_samples); a wave scans the *wave_symbols symbols k with equal k / *wave_symbols (64; 512 at decim 1,
+ * where a lane owns eight consecutive symbols); the defaults of region_symbols and warmup_symbols. */
+int bbb_dfe_geometry(uint32_t decim, uint64_t *step_samples, uint64_t *step_symbols, uint64_t *wave_symbols,
+                     uint64_t *region_symbols, uint64_t *warmup_symbols);
+/* The definition as a plain serial loop over host memory (works without a GPU): in[-1] .. in[-nbefore] readable, *state the
+ * state word (read and written), bits_packed / soft / *nbits_out as in bbb_dfe_run. */
+int bbb_dfe_model_host(const int16_t *in, uint64_t nin, uint32_t nbefore, const bbb_dfe_cfg *cfg, uint32_t *state,
+                       uint64_t *bits_packed, void *soft, uint64_t *nbits_out);
+
 /* ---- the filtered link: eye, bathtub and BER sweep behind a receive filter (rx.py:24-26) -------------------------------- */
 
 /* What bbb_tx_eye_run and bbb_tx_ber_sweep_run give for the raw sample, for the sample AFTER the receive filter, the
