@@ -2,6 +2,7 @@
 // Host logic only: argument checks, GF(2) jump-ahead plans, workspace, kernel launches.
 #include "bbb_common.hpp"
 #include "dev_buf.hpp"
+#include "event.hpp"
 #include "capture.hpp"
 #include "awgn_launch.hpp"
 #include "stage_common.hpp"
@@ -54,23 +55,6 @@ int use_device(int device) {
 }
 
 namespace {
-
-// An owned event; the destructor destroys it.  An ordering event (hipEventDisableTiming) is created by its first record, so
-// a host-only handle creates none; an event that bbb_lutopt_profile reads times between is created by create_timed().
-struct Event {
-    hipEvent_t e = nullptr;
-    Event() = default;
-    Event(Event &&o) noexcept : e(o.e) { o.e = nullptr; }
-    Event &operator=(Event &&o) noexcept { std::swap(e, o.e); return *this; }      // (o destroys the old one)
-    ~Event() { if (e) (void)hipEventDestroy(e); }
-    operator hipEvent_t() const { return e; }
-    int create_timed() { BBB_HIP(hipEventCreate(&e)); return BBB_OK; }
-    int record(hipStream_t s) {
-        if (!e) BBB_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        BBB_HIP(hipEventRecord(e, s));
-        return BBB_OK;
-    }
-};
 
 // Device buffers and the event behind the last kernel that read them (read_pending: one has since the last grow).  A writer
 // on another stream waits for that reader; growing frees the old buffers, so the host first synchronises with it.

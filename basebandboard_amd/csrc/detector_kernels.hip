@@ -18,9 +18,9 @@
 // State per lane: two 32-bit registers (k <= 31), a counter and the input register; the work is
 // integer VALU (about 16 lane-ops per clock), HBM traffic is 1/8 B read + 2/8 B written per bit.
 #include "bbb_common.hpp"
+#include "detector_launch.hpp"
 
-#include <mutex>
-#include <vector>
+#include <type_traits>
 
 namespace bbb {
 
@@ -37,6 +37,7 @@ __host__ __device__ constexpr int det_tap_of(int k) {
 }
 
 struct DetCount { u64 err_synced, err_raw, reload_clocks, resyncs; };
+static_assert(sizeof(DetState) == kDetStateBytes && sizeof(DetCount) == kDetCountBytes, "detector_launch.hpp lays the workspace out by these");
 
 // 64 (or `nvalid` < 64) clocks on input word w.  Output bit i of errw / rlw = `err` / `reload` sampled
 // after clock i, what the reference testbench reads (prbs.py:146-150).  All one-bit signals are kept as
@@ -627,8 +628,7 @@ det_sparse_kernel(const u64 *__restrict src, const u64 *__restrict flags, u64 nb
 // then run their chunks from those flags.  The classification of one wave overlaps the serial part of the others on the same
 // CU (latency-bound lanes beside a memory-bound stream), the flags never travel through memory, and the few words a lane
 // goes back to were read by its own wave microseconds earlier.  Needs chunks of whole 128-word flag blocks and a warm-up of
-// at most one; other geometries take the two kernels above.
-constexpr int kDetFusedMaxChunkWords = 1024;
+// at most one; other geometries take the two kernels above.  (kDetFusedMaxChunkWords: detector_launch.hpp)
 template <int K>
 __global__ void __launch_bounds__(256)
 det_fused_kernel(const u64 *__restrict src, u64 nbits, u64 nwords, u64 chunk_words, u64 warm_words, u64 nchunks,
@@ -861,296 +861,87 @@ det_reduce_kernel(u64 nchunks, const DetCount *__restrict counts, u64 *__restric
     }
 }
 
-// The call's device workspace and its pinned read-back buffer, kept between calls (grow-only, one per concurrent call and
-// device).  With a stream-ordered allocation per call the pool gave the 22 MB of a 1e10-bit call back to the driver at every
-// synchronisation and fetched them again at the next call, and the totals came back through a pageable bounce buffer: 0.26 ms
-// of host time around 0.49 ms of kernels.
-// zeroed_at / ev_zero: the 16 tail words at that offset of d are zero once ev_zero has happened -- a call that ends the plain way
-// zeroes them for the next one BEHIND its read-back instead of the next call doing so in front of its first kernel
-struct DetWorkspace { int dev; char *d; size_t cap; u64 *h; bool busy; hipEvent_t ev_copy, ev_zero; size_t zeroed_at; bool zeroed; };
-static std::mutex g_det_ws_mu;
-static std::vector<DetWorkspace> g_det_ws;
-
-static int det_ws_acquire(size_t need, int *slot) {
-    int dev = 0;
-    BBB_HIP(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> g(g_det_ws_mu);
-    int found = -1;
-    for (size_t i = 0; i < g_det_ws.size(); i++)
-        if (!g_det_ws[i].busy && g_det_ws[i].dev == dev) { found = (int)i; break; }
-    if (found < 0) {
-        DetWorkspace w{dev, nullptr, 0, nullptr, false, nullptr, nullptr, 0, false};
-        BBB_HIP(hipHostMalloc((void **)&w.h, 16 * sizeof(u64), hipHostMallocDefault));
-        BBB_HIP(hipEventCreateWithFlags(&w.ev_copy, hipEventDisableTiming));
-        BBB_HIP(hipEventCreateWithFlags(&w.ev_zero, hipEventDisableTiming));
-        g_det_ws.push_back(w);
-        found = (int)g_det_ws.size() - 1;
+// ---------------------------------------------------------------------------------------------
+// The launchers of detector_launch.hpp: what detector_api.hip queues.  The one switch over k hands its K to a generic lambda.
+// ---------------------------------------------------------------------------------------------
+template <class F>
+static int det_with_k(int k, F &&f) {
+    switch (k) {
+    case 7: return f(std::integral_constant<int, 7>{});
+    case 9: return f(std::integral_constant<int, 9>{});
+    case 11: return f(std::integral_constant<int, 11>{});
+    case 15: return f(std::integral_constant<int, 15>{});
+    case 20: return f(std::integral_constant<int, 20>{});
+    case 23: return f(std::integral_constant<int, 23>{});
+    default: return f(std::integral_constant<int, 31>{});
     }
-    DetWorkspace &w = g_det_ws[found];
-    if (w.cap < need) {
-        if (w.d) (void)hipFree(w.d);
-        w.d = nullptr; w.cap = 0; w.zeroed = false;
-        BBB_HIP(hipMalloc((void **)&w.d, need));
-        w.cap = need;
-    }
-    w.busy = true;
-    *slot = found;
-    return BBB_OK;
 }
 
-static void det_ws_release(int slot) {
-    std::lock_guard<std::mutex> g(g_det_ws_mu);
-    DetWorkspace &w = g_det_ws[slot];
-    if (w.cap > (size_t)256 << 20) {        // (a very long stream's workspace is not kept: 256 MiB = 1.2e11 bits at the default chunking)
-        (void)hipFree(w.d);
-        w.d = nullptr; w.cap = 0; w.zeroed = false;
-    }
-    w.busy = false;
+bool det_k_ok(int k) { return det_tap_of(k) != 0; }
+bool det_sparse_ok(int k) {                       // (K = 20: ten history words -- the dense pass)
+    return det_with_k(k, [](auto kc) { return (int)DetLag<decltype(kc)::value>::OK; }) != 0;
 }
 
-template <int K>
-static int detector_stream_k(const u64 *src, u64 nbits, u64 *err, u64 *reload, bbb_detector_stats *stats, u64 chunk_bits,
-                             u64 warm_bits, hipStream_t st) {
-    const u64 nwords = (nbits + 63) / 64;
-    const u64 chunk_words = chunk_bits / 64, warm_words = (warm_bits + 63) / 64;
-    const u64 nchunks = (nwords + chunk_words - 1) / chunk_words;
-    if (nchunks > 0x7fffffffull) return fail(BBB_EINVAL, "too many chunks; raise chunk_bits");
-    // one stream-ordered allocation: spec | endst | counts | list | nlist + totals
-    constexpr bool kSparse = DetLag<K>::OK;             // (K = 20: ten history words -- the dense pass)
-    const size_t o_spec = 0, o_end = o_spec + nchunks * sizeof(DetState), o_cnt = o_end + nchunks * sizeof(DetState),
-                 o_list = o_cnt + nchunks * sizeof(DetCount), o_tail = (o_list + 2 * nchunks * sizeof(unsigned) + 7) & ~(size_t)7,
-                 o_flags = (o_tail + 16 * sizeof(u64) + 15) & ~(size_t)15, total = o_flags + (kSparse ? ((nwords + 255) / 256) * 4 * sizeof(u64) : 0);
-    int ws_slot = -1;
-    int rc_ws = det_ws_acquire(total, &ws_slot);
-    if (rc_ws) return rc_ws;
-    char *ws;
-    u64 *hpin;
-    hipEvent_t ev_copy, ev_zero;
-    bool tail_zeroed, zero_pending;
-    {
-        std::lock_guard<std::mutex> g(g_det_ws_mu);
-        DetWorkspace &w = g_det_ws[ws_slot];
-        ws = w.d; hpin = w.h; ev_copy = w.ev_copy; ev_zero = w.ev_zero;
-        tail_zeroed = w.zeroed && w.zeroed_at == o_tail;
-        zero_pending = w.zeroed;
-        w.zeroed = false;                     // (until this call has ended the way that leaves them zeroed again)
-    }
-    // The previous user of this workspace left a 128-byte memset queued behind its read-back (ev_zero) and handed the workspace back
-    // without waiting for it.  A call with ANOTHER layout (other nbits or chunking: the old tail lies inside this call's chunk
-    // records), on another stream, must not start before that memset has run -- round 4's advisor: a late memset zeroing 16 words
-    // of the new call's records.  Whoever finds the flag set waits for the event first (same stream: nothing to wait for).
-    if (zero_pending) (void)hipStreamWaitEvent(st, ev_zero, 0);
-    DetState *spec = (DetState *)(ws + o_spec), *endst = (DetState *)(ws + o_end);
-    DetCount *counts = (DetCount *)(ws + o_cnt);
-    unsigned *list = (unsigned *)(ws + o_list), *list2 = list + nchunks;
-    u64 *tail = (u64 *)(ws + o_tail), *tail2 = tail + 8;       // tail[0..3] totals, low half of tail[4] = number of bad chunks
-    unsigned *nlist = (unsigned *)(tail + 4), *nlist2 = (unsigned *)(tail2 + 4);
-    // (every path below has synchronised the stream before it calls this, or failed in a HIP call and does so here)
-    auto cleanup = [&]() { (void)hipStreamSynchronize(st); det_ws_release(ws_slot); };
-    const unsigned grid = (unsigned)((nchunks + 255) / 256);
-    // (the reduce kernel's time is its atomics -- one per block and counter: 512 blocks 11 us, 128 blocks 6 us, 64 too few to
-    // stream 20 MB of chunk records; BBB_DET_RGRID: A/B timing, -DBBB_EXPERIMENTS only)
-    const unsigned rmax = (unsigned)env_knob("BBB_DET_RGRID", 128);
-    const unsigned rgrid = grid < rmax ? grid : rmax;
-    // cooperative 128-byte loads need chunks and warm-up in whole 16-word rows on 16-byte aligned data
-    const int tiles_ok = chunk_words % 16 == 0 && warm_words % 16 == 0 && warm_words > 0 && ((uintptr_t)src & 15) == 0;
-    static const bool dense = env_knob("BBB_DET_DENSE", 0) != 0;          // (A/B timing of the two forms; -DBBB_EXPERIMENTS only)
-    const bool sparse = kSparse && !dense && ((uintptr_t)src & 15) == 0;
-    if (sparse) {
-        if constexpr (kSparse) {
-            u64 *flags = (u64 *)(ws + o_flags);
-            if (err) (void)hipMemsetAsync(err, 0, nwords * sizeof(u64), st);
-            if (reload) (void)hipMemsetAsync(reload, 0, nwords * sizeof(u64), st);
-            const u64 nblk = (nwords + 255) / 256;                        // one wave per 256 words, four waves per block
-            const unsigned cgrid = (unsigned)((nblk + 3) / 4 < 8192 ? (nblk + 3) / 4 : 8192);
-            static const bool two_kernels = env_knob("BBB_DET_TWO_KERNELS", 0) != 0;      // (A/B timing; -DBBB_EXPERIMENTS only)
-            if (chunk_words % 128 == 0 && chunk_words <= (u64)kDetFusedMaxChunkWords && warm_words <= 128 && !two_kernels) {
+static const u64 *det_in(const uint64_t *p) { return reinterpret_cast<const u64 *>(p); }
+static u64 *det_out(uint64_t *p) { return reinterpret_cast<u64 *>(p); }
+
+int det_first_pass_launch(int k, DetForm form, const DetLaunch &a, unsigned grid, unsigned cgrid, hipStream_t st) {
+    const u64 *src = det_in(a.src);
+    u64 *err = det_out(a.err), *reload = det_out(a.reload), *flags = det_out(a.flags);
+    const u64 nbits = a.nbits, nwords = a.nwords, chunk_words = a.chunk_words, warm_words = a.warm_words, nchunks = a.nchunks;
+    DetState *spec = a.spec, *endst = a.endst;
+    DetCount *counts = a.counts;
+    const int tiles_ok = a.tiles_ok;
+    return det_with_k(k, [&](auto kc) {
+        constexpr int K = decltype(kc)::value;
+        switch (form) {
+        case kDetFused:
+            if constexpr (DetLag<K>::OK)
                 hipLaunchKernelGGL(det_fused_kernel<K>, dim3(grid), dim3(256), 4 * (chunk_words + 8) * sizeof(u64), st, src, nbits, nwords, chunk_words,
                                    warm_words, nchunks, spec, endst, counts, err, reload);
-            } else {
+            break;
+        case kDetTwoKernels:
+            if constexpr (DetLag<K>::OK) {
                 hipLaunchKernelGGL(det_classify_kernel<K>, dim3(cgrid), dim3(256), 0, st, src, nbits, nwords, flags);
                 hipLaunchKernelGGL(det_sparse_kernel<K>, dim3(grid), dim3(256), 0, st, src, (const u64 *)flags, nbits, nwords, chunk_words,
                                    warm_words, nchunks, spec, endst, counts, err, reload);
             }
+            break;
+        case kDetDenseOut:
+            hipLaunchKernelGGL((det_chunk_kernel<K, true>), dim3(grid), dim3(256), 0, st, 0, src, nbits, nwords, chunk_words, warm_words,
+                               nchunks, (const unsigned *)nullptr, 0u, spec, endst, counts, err, reload, tiles_ok, (const unsigned *)nullptr);
+            break;
+        case kDetDenseTotals:
+            hipLaunchKernelGGL((det_chunk_kernel<K, false>), dim3(grid), dim3(256), 0, st, 0, src, nbits, nwords, chunk_words, warm_words,
+                               nchunks, (const unsigned *)nullptr, 0u, spec, endst, counts, err, reload, tiles_ok, (const unsigned *)nullptr);
+            break;
         }
-    } else if (err || reload)
-        hipLaunchKernelGGL((det_chunk_kernel<K, true>), dim3(grid), dim3(256), 0, st, 0, src, nbits, nwords, chunk_words, warm_words,
-                           nchunks, (const unsigned *)nullptr, 0u, spec, endst, counts, err, reload, tiles_ok, (const unsigned *)nullptr);
-    else
-        hipLaunchKernelGGL((det_chunk_kernel<K, false>), dim3(grid), dim3(256), 0, st, 0, src, nbits, nwords, chunk_words, warm_words,
-                           nchunks, (const unsigned *)nullptr, 0u, spec, endst, counts, err, reload, tiles_ok, (const unsigned *)nullptr);
-    u64 rerun = 0, passes = 0;
-    bool serial = false;
-    u64 h[5] = {0, 0, 0, 0, 0};
-    if (env_knob("BBB_DET_ONE_TRIP", 1)) {
-        // ONE round trip for the two common outcomes: the chain is consistent as speculated, or it is after the few
-        // inconsistent chunks have been run again from their predecessors' end states.  Verify + totals (pass 1), a re-run
-        // of at most kSpec listed chunks whose count the device reads itself, verify + totals again (pass 2, which returns
-        // at once when pass 1 found nothing) -- all queued before the host looks.
-        constexpr unsigned kSpec = 4096;
-        u64 *const hh = hpin;
-        if (!tail_zeroed) (void)hipMemsetAsync(tail, 0, 16 * sizeof(u64), st);      // (else: zeroed behind the previous call's read-back; waited for above)
-        hipLaunchKernelGGL(det_reduce_kernel, dim3(rgrid), dim3(256), 0, st, nchunks, counts, tail, (const DetState *)spec,
-                           (const DetState *)endst, list, nlist, (const unsigned *)nullptr);
-        // The repair stages are queued blind only for the dense pass, whose reset-state speculation leaves a few dozen
-        // inconsistent chunks on every noisy stream.  The sparse pass starts a chunk from the clean state its flags imply and
-        // is consistent as speculated unless an error or a reload sits right on a chunk boundary: there the two idle launches
-        // (10 us of a 0.3 ms call) cost more than the second round trip they save, so the host looks first.
-        if (!sparse) {
-            hipLaunchKernelGGL((det_chunk_kernel<K, true>), dim3(kSpec / 256), dim3(256), 0, st, 1, src, nbits, nwords, chunk_words, warm_words,
-                               nchunks, (const unsigned *)list, kSpec, spec, endst, counts, err, reload, 0, (const unsigned *)nlist);
-            hipLaunchKernelGGL(det_reduce_kernel, dim3(rgrid), dim3(256), 0, st, nchunks, counts, tail2, (const DetState *)spec,
-                               (const DetState *)endst, list2, nlist2, (const unsigned *)nlist);
-        }
-        hipError_t e = hipMemcpyAsync(hh, tail, 16 * sizeof(u64), hipMemcpyDeviceToHost, st);
-        // The host waits for the read-back only; the zeroing of the tail words for the NEXT call is queued behind it and runs
-        // while the host returns (5 us of a 0.29 ms call that were in front of the first kernel)
-        bool zero_queued = false;
-        if (e == hipSuccess && sparse) {
-            e = hipEventRecord(ev_copy, st);
-            if (e == hipSuccess) e = hipMemsetAsync(tail, 0, 16 * sizeof(u64), st);
-            if (e == hipSuccess) e = hipEventRecord(ev_zero, st);
-            zero_queued = e == hipSuccess;
-            if (e == hipSuccess) e = hipEventSynchronize(ev_copy);
-        } else if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) { cleanup(); BBB_HIP(e); }
-        const unsigned nbad1 = (unsigned)(hh[4] & 0xffffffffull), nbad2 = (unsigned)(hh[12] & 0xffffffffull);
-        bool settled = false;
-        if (!nbad1) {
-            for (int i = 0; i < 5; i++) h[i] = hh[i];
-            settled = true;
-            if (zero_queued) {
-                // (nothing of this call but that memset is in flight: the workspace goes back without a stream synchronisation)
-                {
-                    std::lock_guard<std::mutex> g(g_det_ws_mu);
-                    g_det_ws[ws_slot].zeroed = true; g_det_ws[ws_slot].zeroed_at = o_tail;
-                }
-                det_ws_release(ws_slot);
-                BBB_HIP(hipGetLastError());
-                if (stats) {
-                    stats->bits = nbits; stats->errors = h[0]; stats->errors_raw = h[1]; stats->reload_clocks = h[2];
-                    stats->resyncs = h[3]; stats->chunks = nchunks; stats->chunks_rerun = 0; stats->serial_fallback = 0;
-                }
-                return BBB_OK;
-            }
-        }
-        else if (sparse) {
-            // second trip: the listed chunks again from their predecessors' ends, verify + totals, look again
-            const unsigned nb = nbad1 < kSpec ? nbad1 : kSpec;
-            hipLaunchKernelGGL((det_chunk_kernel<K, true>), dim3((nb + 255) / 256), dim3(256), 0, st, 1, src, nbits, nwords, chunk_words,
-                               warm_words, nchunks, (const unsigned *)list, nb, spec, endst, counts, err, reload, 0, (const unsigned *)nullptr);
-            hipLaunchKernelGGL(det_reduce_kernel, dim3(rgrid), dim3(256), 0, st, nchunks, counts, tail2, (const DetState *)spec,
-                               (const DetState *)endst, list2, nlist2, (const unsigned *)nullptr);
-            e = hipMemcpyAsync(hh, tail, 16 * sizeof(u64), hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess) e = hipStreamSynchronize(st);
-            if (e != hipSuccess) { cleanup(); BBB_HIP(e); }
-            rerun += nb;
-            passes = 1;
-            if (nbad1 <= kSpec && !(unsigned)(hh[12] & 0xffffffffull)) { for (int i = 0; i < 5; i++) h[i] = hh[8 + i]; settled = true; }
-        } else {
-            rerun += nbad1 < kSpec ? nbad1 : kSpec;
-            passes = 1;
-            if (nbad1 <= kSpec && !nbad2) { for (int i = 0; i < 5; i++) h[i] = hh[8 + i]; settled = true; }
-        }
-        if (settled) {
-            cleanup();
-            BBB_HIP(hipGetLastError());
-            if (stats) {
-                stats->bits = nbits; stats->errors = h[0]; stats->errors_raw = h[1]; stats->reload_clocks = h[2];
-                stats->resyncs = h[3]; stats->chunks = nchunks; stats->chunks_rerun = rerun; stats->serial_fallback = 0;
-            }
-            return BBB_OK;
-        }
-    }
-    for (;;) {
-        // verify, and reduce at once in the hope that the chain is already consistent: one round trip
-        (void)hipMemsetAsync(tail, 0, 5 * sizeof(u64), st);
-        hipLaunchKernelGGL(det_reduce_kernel, dim3(rgrid), dim3(256), 0, st, nchunks, counts, tail, (const DetState *)spec,
-                           (const DetState *)endst, list, nlist, (const unsigned *)nullptr);
-        hipError_t e = hipMemcpyAsync(h, tail, sizeof h, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) { cleanup(); BBB_HIP(e); }
-        const unsigned nbad = (unsigned)(h[4] & 0xffffffffull);
-        if (!nbad) break;
-        passes++;
-        if (passes > 32) {
-            // the speculation does not settle on this stream: continue serially from the first bad chunk
-            std::vector<unsigned> hb(nbad);
-            e = hipMemcpy(hb.data(), list, nbad * sizeof(unsigned), hipMemcpyDeviceToHost);
-            if (e != hipSuccess) { cleanup(); BBB_HIP(e); }
-            unsigned c0 = hb[0];
-            for (unsigned x : hb) c0 = x < c0 ? x : c0;
-            hipLaunchKernelGGL(det_serial_kernel<K>, dim3(1), dim3(64), 0, st, src, nbits, nwords, chunk_words, nchunks, (u64)c0,
-                               spec, endst, counts, err, reload);
-            serial = true;
-            passes = 0;                     // the serial kernel stops where the chain is consistent again: verify anew
-            rerun += 1;
-            continue;
-        }
-        rerun += nbad;
-        hipLaunchKernelGGL((det_chunk_kernel<K, true>), dim3((nbad + 255) / 256), dim3(256), 0, st, 1, src, nbits, nwords, chunk_words,
-                           warm_words, nchunks, (const unsigned *)list, nbad, spec, endst, counts, err, reload, 0, (const unsigned *)nullptr);
-    }
-    cleanup();
-    BBB_HIP(hipGetLastError());
-    if (stats) {
-        stats->bits = nbits;
-        stats->errors = h[0];
-        stats->errors_raw = h[1];
-        stats->reload_clocks = h[2];
-        stats->resyncs = h[3];
-        stats->chunks = nchunks;
-        stats->chunks_rerun = rerun;
-        stats->serial_fallback = serial ? 1 : 0;
-    }
+        return (int)BBB_OK;
+    });
+}
+
+int det_reduce_launch(const DetLaunch &a, unsigned rgrid, uint64_t *totals, unsigned *list, unsigned *nlist, const unsigned *skip_if_zero,
+                      hipStream_t st) {
+    hipLaunchKernelGGL(det_reduce_kernel, dim3(rgrid), dim3(256), 0, st, (u64)a.nchunks, (const DetCount *)a.counts, det_out(totals),
+                       (const DetState *)a.spec, (const DetState *)a.endst, list, nlist, skip_if_zero);
     return BBB_OK;
 }
 
-int prbs_detector_stream_launch(int k, const uint64_t *src, uint64_t nbits, uint64_t *err, uint64_t *reload,
-                                bbb_detector_stats *stats, uint64_t chunk_bits, uint64_t warm_bits, hipStream_t st) {
-    if (!det_tap_of(k)) return fail(BBB_EINVAL, "k=" + std::to_string(k) + " invalid for PRBS");
-    if (chunk_bits == 0) {
-        // about four waves of lanes per SIMD, but chunks of 4096 ... 32768 bits: the warm-up before every chunk is
-        // 1024 bits of extra work, and short inputs should still fill the device.  (Sizing the chunks so that they fill
-        // whole generations of resident lanes -- 2 x 38912-bit chunks per lane slot at 1e10 bits instead of 2.33 x 32768 --
-        // changed nothing measurable: 0.455-0.46 ms either way.)
-        const uint64_t want = (nbits / 262144 + 127) / 128 * 128;
-        chunk_bits = want < 4096 ? 4096 : (want > 32768 ? 32768 : want);
-        if (want > 32768) {
-            // Long streams (round 5; profiles/r05_det_chunk_sweep.log): the fused kernel takes chunks of 512 ... 1024 words, a block
-            // four waves x 64 chunks, and all blocks are resident at once -- the kernel then takes as long as the CU with the MOST
-            // blocks, so the chunk length is chosen for the smallest (blocks on the fullest CU) x (words per chunk); ties go to the
-            // longer chunk (fewer chunk records, fewer speculative starts).  1e10 bits: 640 words (954 blocks on 256 CUs: 4 x 640)
-            // where round 4's fixed 512 gave 1192 blocks (5 x 512): 0.277 -> 0.258 ms per call.
-            int dev = 0, ncu = 256;
-            if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu < 1) ncu = 256;
-            const uint64_t nwords = (nbits + 63) / 64;
-            uint64_t best_cost = ~0ull, best_cw = 512;
-            for (uint64_t cw = 512; cw <= (uint64_t)kDetFusedMaxChunkWords; cw += 128) {
-                const uint64_t nblocks = ((nwords + cw - 1) / cw + 255) / 256;
-                const uint64_t cost = ((nblocks + (uint64_t)ncu - 1) / (uint64_t)ncu) * cw;
-                if (cost <= best_cost) { best_cost = cost; best_cw = cw; }
-            }
-            chunk_bits = best_cw * 64;
-        }
-    }
-    if (warm_bits == 0) warm_bits = 1024;
-    if (chunk_bits % 64) return fail(BBB_EINVAL, "chunk_bits must be a multiple of 64");
-    if (nbits == 0) {
-        if (stats) *stats = bbb_detector_stats{};
-        return BBB_OK;
-    }
-    const u64 *s = reinterpret_cast<const u64 *>(src);
-    u64 *e = reinterpret_cast<u64 *>(err), *r = reinterpret_cast<u64 *>(reload);
-    switch (k) {
-    case 7: return detector_stream_k<7>(s, nbits, e, r, stats, chunk_bits, warm_bits, st);
-    case 9: return detector_stream_k<9>(s, nbits, e, r, stats, chunk_bits, warm_bits, st);
-    case 11: return detector_stream_k<11>(s, nbits, e, r, stats, chunk_bits, warm_bits, st);
-    case 15: return detector_stream_k<15>(s, nbits, e, r, stats, chunk_bits, warm_bits, st);
-    case 20: return detector_stream_k<20>(s, nbits, e, r, stats, chunk_bits, warm_bits, st);
-    case 23: return detector_stream_k<23>(s, nbits, e, r, stats, chunk_bits, warm_bits, st);
-    default: return detector_stream_k<31>(s, nbits, e, r, stats, chunk_bits, warm_bits, st);
-    }
+int det_rerun_launch(int k, const DetLaunch &a, unsigned grid, const unsigned *list, unsigned nlist, const unsigned *nlist_dev, hipStream_t st) {
+    return det_with_k(k, [&](auto kc) {
+        hipLaunchKernelGGL((det_chunk_kernel<decltype(kc)::value, true>), dim3(grid), dim3(256), 0, st, 1, det_in(a.src), (u64)a.nbits, (u64)a.nwords,
+                           (u64)a.chunk_words, (u64)a.warm_words, (u64)a.nchunks, list, nlist, a.spec, a.endst, a.counts, det_out(a.err),
+                           det_out(a.reload), 0, nlist_dev);
+        return (int)BBB_OK;
+    });
+}
+
+int det_serial_launch(int k, const DetLaunch &a, uint64_t c0, hipStream_t st) {
+    return det_with_k(k, [&](auto kc) {
+        hipLaunchKernelGGL(det_serial_kernel<decltype(kc)::value>, dim3(1), dim3(64), 0, st, det_in(a.src), (u64)a.nbits, (u64)a.nwords,
+                           (u64)a.chunk_words, (u64)a.nchunks, (u64)c0, a.spec, a.endst, a.counts, det_out(a.err), det_out(a.reload));
+        return (int)BBB_OK;
+    });
 }
 
 }  // namespace bbb

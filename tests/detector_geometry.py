@@ -1,6 +1,7 @@
-"""What bbb_prbs_detector_stream does with a call's geometry, restated from detector_kernels.hip for the tests
-(test_detector_geometry_host.py holds this restatement to the kernel file's text; test_gpu_detector_forms.py uses
-it to name the form each of its cells is meant to take).  Nothing here is read by the product."""
+"""What bbb_prbs_detector_stream does with a call's geometry, restated from detector_api.hip (det_plan) and detector_kernels.hip
+for the tests (test_detector_geometry_host.py holds this restatement to the text of those files, test_sched_model_detector.py to
+what det_plan returns; test_gpu_detector_forms.py uses it to name the form each of its cells is meant to take).  Nothing here
+is read by the product."""
 
 KS = (7, 9, 11, 15, 20, 23, 31)
 TAPS = {7: 6, 9: 5, 11: 9, 15: 14, 20: 3, 23: 18, 31: 28}            # det_tap_of (prbs.py:14)
@@ -18,7 +19,7 @@ def det_lag(k):
 
 
 def default_chunk_words(nbits, ncu=256):
-    """prbs_detector_stream_launch with chunk_bits == 0."""
+    """det_plan (detector_api.hip) with chunk_bits == 0."""
     want = (nbits // 262144 + 127) // 128 * 128
     chunk_bits = 4096 if want < 4096 else (32768 if want > 32768 else want)
     if want > 32768:
@@ -34,7 +35,7 @@ def default_chunk_words(nbits, ncu=256):
 
 
 def form_of(k, chunk_words, warm_bits, aligned16=True):
-    """The execution form detector_stream_k takes: 'fused', 'two-kernel', 'dense-tiled' (tiles offered: a wave with 64
+    """The execution form det_plan (detector_api.hip) chooses: 'fused', 'two-kernel', 'dense-tiled' (tiles offered: a wave with 64
     full chunks behind a full warm-up takes them) or 'dense-lane'."""
     warm_words = (warm_bits + 63) // 64
     if det_lag(k)["OK"] and aligned16:

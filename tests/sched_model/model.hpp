@@ -29,6 +29,11 @@ uint64_t ops_checked();
 uint64_t transcript();                            // the running hash over everything logged so far (model.cpp)
 void fail_nth_launch(int nth);                    // the nth kernel-launch stub from now on returns BBB_EHIP, once (0: none does)
 bool launch_failure_pending();                    // ... and has not done so yet
+bool refused();                                   // a launch stub asks first: true means queue nothing and return BBB_EHIP
+// what the next device-to-host copies deliver instead of zeros: one entry per copy, in order (a shorter entry: zeros behind it)
+void deliver_next_d2h(const void *bytes, size_t n);
+size_t deliveries_pending();
+void clear_deliveries();                          // (a call that returned early left some unread)
 
 // " (a, b, ...)": a launch stub's scalar arguments, appended to its operation text so that the transcript covers them
 template <typename... T>

@@ -1,6 +1,7 @@
-"""tests/detector_geometry.py restates constants and rules of detector_kernels.hip for the GPU form matrix
-(test_gpu_detector_forms.py).  This file makes drift loud: it reads the kernel file as text and holds the restatement
-to it, and it checks the word recurrence the sparse forms rest on against the oracle's PRBS, in plain integers.
+"""tests/detector_geometry.py restates constants and rules of the stream detector -- detector_kernels.hip (the kernels and their
+launchers), detector_launch.hpp (what the kernel file exports) and detector_api.hip (the host scheduler and its det_plan) -- for
+the GPU form matrix (test_gpu_detector_forms.py).  This file makes drift loud: it reads the three files as text and holds the
+restatement to them, and it checks the word recurrence the sparse forms rest on against the oracle's PRBS, in plain integers.
 It is also the one place that lists which template instantiations exist."""
 import pathlib
 import re
@@ -10,7 +11,10 @@ import pytest
 from detector_geometry import (FUSED_MAX_CHUNK_WORDS, KS, TAPS, default_chunk_words, delayed_words, det_lag, form_of, last_term_holds,
                                word_recurrence_holds)
 
-SRC = (pathlib.Path(__file__).resolve().parent.parent / "basebandboard_amd" / "csrc" / "detector_kernels.hip").read_text()
+CSRC = pathlib.Path(__file__).resolve().parent.parent / "basebandboard_amd" / "csrc"
+SRC = (CSRC / "detector_kernels.hip").read_text()          # the kernels, DetLag, det_tap_of, the launchers and their switch over k
+HDR = (CSRC / "detector_launch.hpp").read_text()           # what the kernel file exports to the host file
+API = (CSRC / "detector_api.hip").read_text()              # the scheduler: det_plan holds the geometry
 SPARSE_KS = (7, 9, 11, 15, 23, 31)
 
 
@@ -19,7 +23,7 @@ def squeeze(s):
 
 
 def test_constants_of_the_kernel_file():
-    assert f"constexpr int kDetFusedMaxChunkWords = {FUSED_MAX_CHUNK_WORDS};" in SRC and FUSED_MAX_CHUNK_WORDS == 1024
+    assert f"constexpr int kDetFusedMaxChunkWords = {FUSED_MAX_CHUNK_WORDS};" in HDR and FUSED_MAX_CHUNK_WORDS == 1024
     taps = re.search(r"det_tap_of\(int k\) \{\s*return (.*?);", SRC).group(1)
     assert {int(a): int(b) for a, b in re.findall(r"k == (\d+) \? (\d+)", taps)} == TAPS
     # DetLag: M by the tap, the lags, the history length and the rule for OK
@@ -28,20 +32,22 @@ def test_constants_of_the_kernel_file():
 
 
 def test_form_selection_of_the_kernel_file():
-    """The conditions detector_geometry.form_of restates, as they stand in detector_stream_k."""
-    s = squeeze(SRC)
+    """The conditions detector_geometry.form_of restates, as they stand in det_plan and, for the tiles, in det_chunk_kernel."""
+    s = squeeze(API)
     assert "if (chunk_words % 128 == 0 && chunk_words <= (u64)kDetFusedMaxChunkWords && warm_words <= 128 && !two_kernels)" in s
     assert "const bool sparse = kSparse && !dense && ((uintptr_t)src & 15) == 0;" in s
-    assert "constexpr bool kSparse = DetLag<K>::OK;" in s
+    # (what exports DetLag<K>::OK to the host: the kernel file's det_sparse_ok, and det_plan's use of it)
+    assert "const bool kSparse = det_sparse_ok(k);" in s
+    assert "bool det_sparse_ok(int k) {" in SRC and "return (int)DetLag<decltype(kc)::value>::OK;" in squeeze(SRC)
     assert "const int tiles_ok = chunk_words % 16 == 0 && warm_words % 16 == 0 && warm_words > 0 && ((uintptr_t)src & 15) == 0;" in s
-    assert "if (tiles_ok && c0 + 64 <= nchunks && c0 * chunk_words >= warm_words && (c0 + 64) * chunk_words * 64 <= nbits)" in s
+    assert "if (tiles_ok && c0 + 64 <= nchunks && c0 * chunk_words >= warm_words && (c0 + 64) * chunk_words * 64 <= nbits)" in squeeze(SRC)
     assert "const u64 chunk_words = chunk_bits / 64, warm_words = (warm_bits + 63) / 64;" in s
     # the knobs that could send a call another way exist in the experiments build only
     assert "BBB_EXPERIMENTS" in (pathlib.Path(__file__).resolve().parent.parent / "basebandboard_amd" / "csrc" / "bbb_common.hpp").read_text()
 
 
 def test_default_chunk_rule_of_the_kernel_file():
-    s = squeeze(SRC)
+    s = squeeze(API)
     assert "const uint64_t want = (nbits / 262144 + 127) / 128 * 128;" in s
     assert "chunk_bits = want < 4096 ? 4096 : (want > 32768 ? 32768 : want);" in s
     assert "for (uint64_t cw = 512; cw <= (uint64_t)kDetFusedMaxChunkWords; cw += 128) {" in s
@@ -72,10 +78,11 @@ def test_lag_constants_and_instantiations():
     for k in KS:
         lg = det_lag(k)
         assert lg["OK"] == (lg["NH"] <= 3) and lg["LAGT"] >= 64            # every bit of the next word depends on earlier words only
-    # one detector_stream_k<K> per k, and with it det_chunk_kernel<K, true / false>, det_serial_kernel<K>, and for the k with OK
-    # det_fused_kernel<K>, det_classify_kernel<K>, det_sparse_kernel<K>
-    cases = re.findall(r"(?:case (\d+)|default): return detector_stream_k<(\d+)>", SRC)
+    # one case per k in the launchers' one switch, and with it det_chunk_kernel<K, true / false>, det_serial_kernel<K>, and for the
+    # k with OK det_fused_kernel<K>, det_classify_kernel<K>, det_sparse_kernel<K>
+    cases = re.findall(r"(?:case (\d+)|default): return f\(std::integral_constant<int, (\d+)>", SRC)
     assert sorted(int(b) for _, b in cases) == list(KS) and all(a in ("", b) for a, b in cases)
+    assert "detector_stream_k" not in SRC + API and SRC.count("switch (k)") == 1      # the host scheduler is no template on K
     assert "static_assert(NH + 2 <= 5" in SRC                              # det_classify_256: the two lanes below hold the history
 
 

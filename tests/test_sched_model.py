@@ -19,7 +19,8 @@ import pytest
 
 from conftest import ROOT
 
-SRC = [str(ROOT / "tests" / "sched_model" / "model.cpp"), str(ROOT / "tests" / "sched_model" / "driver.cpp")]
+SRC = [str(ROOT / "tests" / "sched_model" / "model.cpp"), str(ROOT / "tests" / "sched_model" / "detector_stub.cpp"),
+       str(ROOT / "tests" / "sched_model" / "driver.cpp")]
 TAPS = str(ROOT / "basebandboard_amd" / "data" / "lutopt_256.taps")
 
 
@@ -160,7 +161,8 @@ def test_a_call_that_fails_at_a_launch_gives_its_timing_events_back(tmp_path):
     r = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
                         "-fno-omit-frame-pointer", "-I", str(ROOT / "tests" / "sched_model"), "-x", "c++",
                         str(ROOT / "basebandboard_amd" / "csrc" / "bbb_api.hip"), "-x", "none",
-                        str(ROOT / "tests" / "sched_model" / "model.cpp"), str(ROOT / "tests" / "sched_model" / "leak_check.cpp"),
+                        str(ROOT / "tests" / "sched_model" / "model.cpp"), str(ROOT / "tests" / "sched_model" / "detector_stub.cpp"),
+                        str(ROOT / "tests" / "sched_model" / "leak_check.cpp"),
                         "-o", str(exe), "-ldl", "-lpthread"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     out = subprocess.run([str(exe), TAPS], capture_output=True, text=True, timeout=300, env={"ASAN_OPTIONS": "detect_leaks=1"})

@@ -44,7 +44,7 @@ def exes(tmp_path_factory):
     text = (CSRC / REBIND).read_text()
     assert text.count(WAIT[0]) == 1, f"the wait of the stream re-binding occurs {text.count(WAIT[0])} times in {REBIND} (expected once)"
     (mut / REBIND).write_text(text.replace(*WAIT))
-    rest = ["-x", "none", str(MODEL / "model.cpp"), str(MODEL / "capture_driver.cpp"), "-ldl", "-lpthread"]
+    rest = ["-x", "none", str(MODEL / "model.cpp"), str(MODEL / "detector_stub.cpp"), str(MODEL / "capture_driver.cpp"), "-ldl", "-lpthread"]
     cmds = {
         "driver": ["g++", "-std=c++17", "-O1", "-g", *SAN, "-I", str(MODEL), "-I", str(CSRC), "-x", "c++", *[str(CSRC / a) for a in API],
                    *rest, "-o", str(d / "driver")],

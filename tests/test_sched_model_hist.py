@@ -33,7 +33,7 @@ def exes(tmp_path_factory):
     d = tmp_path_factory.mktemp("sched_model_hist")
     api = (CSRC / "bbb_api.hip").read_text()
     common = ["-std=c++17", "-O1", "-g", "-I", str(MODEL), "-I", str(CSRC)]
-    rest = ["-x", "c++", str(CSRC / "hist_api.hip"), "-x", "none", str(MODEL / "model.cpp"), str(MODEL / "hist_driver.cpp"), "-ldl", "-lpthread"]
+    rest = ["-x", "c++", str(CSRC / "hist_api.hip"), "-x", "none", str(MODEL / "model.cpp"), str(MODEL / "detector_stub.cpp"), str(MODEL / "hist_driver.cpp"), "-ldl", "-lpthread"]
     procs = {}
     cmd = ["g++", *common, "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer",
            "-x", "c++", str(CSRC / "bbb_api.hip"), *rest, "-o", str(d / "asan")]

@@ -30,7 +30,7 @@ def exes(tmp_path_factory):
     d = tmp_path_factory.mktemp("sched_model_tx_objects")
     cmds = {
         "driver": ["g++", *SAN, "-x", "c++", *[str(CSRC / f) for f in API], "-x", "none", str(MODEL / "model.cpp"),
-                   str(MODEL / "tx_objects_driver.cpp"), "-o", str(d / "driver"), "-ldl", "-lpthread"],
+                   str(MODEL / "detector_stub.cpp"), str(MODEL / "tx_objects_driver.cpp"), "-o", str(d / "driver"), "-ldl", "-lpthread"],
         "bits": ["g++", *SAN, str(MODEL / "tx_bits_check.cpp"), "-o", str(d / "bits")],
     }
     procs = {name: subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True) for name, cmd in cmds.items()}
