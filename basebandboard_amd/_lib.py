@@ -28,6 +28,7 @@ SYMBOLS = [
     "bbb_xcorr_accumulate_i16", "bbb_tx_xcorr_open", "bbb_tx_xcorr_run", "bbb_tx_xcorr_close",
     "bbb_ddc_run", "bbb_ddc_polar_host",
     "bbb_dfe_run", "bbb_dfe_geometry", "bbb_dfe_model_host",
+    "bbb_mlse_plan", "bbb_mlse_run", "bbb_mlse_model_host",
 ]
 
 
@@ -108,6 +109,12 @@ class DfeCfg(C.Structure):
     """bbb_dfe_cfg"""
     _fields_ = [("ff", FirCfg), ("nfb", C.c_uint32), ("fb", C.c_int32 * 4), ("threshold", C.c_int32), ("strict", C.c_uint32),
                 ("region_symbols", C.c_uint32), ("warmup_symbols", C.c_uint32)]
+
+
+class MlseCfg(C.Structure):
+    """bbb_mlse_cfg"""
+    _fields_ = [("ff", FirCfg), ("mem", C.c_uint32), ("g", C.c_int32 * 5), ("init_state", C.c_uint32),
+                ("block_symbols", C.c_uint32), ("warmup_symbols", C.c_uint32), ("lookahead_symbols", C.c_uint32)]
 
 
 class DdcCfg(C.Structure):
@@ -273,6 +280,9 @@ def lib():
     l.bbb_dfe_run.argtypes = [vp, u64, C.c_uint32, C.POINTER(DfeCfg), vp, vp, vp, vp, u64p, i32, vp]
     l.bbb_dfe_geometry.argtypes = [C.c_uint32, u64p, u64p, u64p, u64p, u64p]
     l.bbb_dfe_model_host.argtypes = [vp, u64, C.c_uint32, C.POINTER(DfeCfg), C.POINTER(C.c_uint32), vp, vp, u64p]
+    l.bbb_mlse_plan.argtypes = [C.POINTER(MlseCfg), u64, u64, i32, u64p, u64p, u64p]
+    l.bbb_mlse_run.argtypes = [vp, u64, C.c_uint32, u64, i32, C.POINTER(MlseCfg), vp, vp, u64p, i32, vp]
+    l.bbb_mlse_model_host.argtypes = [vp, u64, C.c_uint32, u64, i32, C.POINTER(MlseCfg), vp, u64p]
     u8p = C.POINTER(C.c_uint8)
     l.bbb_gf2_berlekamp_massey.argtypes = [u8p, u64, u8p, C.POINTER(C.c_int64)]
     l.bbb_gf2_recur.argtypes = [i32, i32, u64p, u8p, i32, u8p]

@@ -193,6 +193,36 @@ def dfe_taps(h, spb, cursor, nff, nfb, noise_power, scale_bits=8):
     return ff, fb, delay
 
 
+def mlse_target(h, spb, cursor, nff, mem, noise_power, shift=None, scale_bits=8):
+    """Filter and target for mlse.MLSE from the MMSE decision-feedback design: (ff, g, shift).
+
+    ff is dfe_taps' feed-forward filter with `mem` feedback taps: it leaves the cursor and the mem bits behind it and
+    suppresses the rest, which is the shortened channel a sequence detector wants.  The target is what the INTEGER filter
+    makes of those bits, in units of y = acc >> shift: g[0] = round(sum_j ff[j] h[cursor - j] / 2^shift), g[i] =
+    round(fb[i - 1] / 2^shift).  shift None: the smallest with sum |g| <= 16383, which leaves a noiseless y a factor of two
+    of headroom in int16.  g is an int64 numpy array of mem + 1 entries."""
+    mem = int(mem)
+    if not 1 <= mem <= 4:
+        raise ValueError("mem must be 1..4")
+    ff, fb, _ = dfe_taps(h, spb, cursor, nff, mem, noise_power, scale_bits)
+    h = np.asarray(h, dtype=np.float64)
+    idx = int(cursor) - np.arange(len(ff), dtype=np.int64)
+    main = float(np.where((idx >= 0) & (idx < len(h)), h[np.clip(idx, 0, len(h) - 1)], 0.0) @ ff.astype(np.float64))
+    raw = np.concatenate([[main], fb.astype(np.float64)])
+
+    def target(s):
+        return np.rint(raw / float(1 << s)).astype(np.int64)
+
+    if shift is None:
+        shift = next((s for s in range(32) if int(np.abs(target(s)).sum()) <= 16383), None)
+        if shift is None:
+            raise ValueError("no shift of 0..31 brings sum |g| to 16383")
+    shift = int(shift)
+    if not 0 <= shift <= 31:
+        raise ValueError("shift must be 0..31")
+    return ff, target(shift), shift
+
+
 def tx_pulse_response(tx, nsamples, nlags=64, first_sample=0, warmup=16, chunk_samples=0):
     """TX.pulse_response: the float64 estimate h[0 .. nlags) of the transmitter's pulse response over a sample range; lag l
     lines up with coefficients[l]."""

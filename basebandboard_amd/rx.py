@@ -30,13 +30,17 @@ class RX:
         self.prbs_k, self.samples_per_bit, self.sample_delay, self.device = prbs_k, int(samples_per_bit), int(sample_delay), int(device)
         self.prbsdet = PRBSErrorDetector(prbs_k, device=device)
 
-    def slice(self, samples, first_sample=0, stride=None, strict=False, rx_filter=None, dfe=None):
+    def slice(self, samples, first_sample=0, stride=None, strict=False, rx_filter=None, dfe=None, mlse=None):
         """Decided bits of an int16 CUDA tensor: bit j = samples[first_sample + sample_delay + j*stride] >= 0
         (`strict`: > 0, the capture script software/memdump/decode.py:15).  Returns (packed int64 tensor, nbits).
         rx_filter (a fir.FIR): the same indices of the filtered stream instead, acc(..) >= 0 (bbb_fir_slice; the
         filtered samples are never stored).
         dfe (a dfe.DFE, out of reset): its decisions at the same indices instead (bbb_dfe_run); the stride is its spb, the
-        threshold and strictness are its own, and it carries its own feed-forward filter, so it excludes rx_filter."""
+        threshold and strictness are its own, and it carries its own feed-forward filter, so it excludes rx_filter.
+        mlse (a mlse.MLSE): the sequence detector's decisions at the same indices instead (bbb_mlse_run, one final call from
+        symbol 0); the stride is its spb.  It excludes dfe and rx_filter."""
+        if mlse is not None and (dfe is not None or rx_filter is not None):
+            raise ValueError("mlse carries its own feed-forward filter and detector: give mlse, dfe or rx_filter, not both")
         if dfe is not None and rx_filter is not None:
             raise ValueError("dfe carries its own feed-forward filter: give dfe or rx_filter, not both")
         if samples.dtype != torch.int16 or not samples.is_cuda or not samples.is_contiguous():
@@ -44,6 +48,12 @@ class RX:
         stride = self.samples_per_bit if stride is None else int(stride)
         phase = int(first_sample) + self.sample_delay
         n = samples.numel()
+        if mlse is not None:
+            if stride != mlse.spb:
+                raise ValueError("the stride must be the mlse's spb")
+            off = min(phase - phase % stride, n)
+            nb = min(off, len(mlse.ff) - 1)
+            return mlse.slice(samples[off - nb:], nbefore=nb, phase=phase % stride)
         if dfe is not None:
             if stride != dfe.spb:
                 raise ValueError("the stride must be the dfe's spb")
@@ -83,17 +93,17 @@ class RX:
             bits, nbits = rx.slice(t, stride=stride, strict=True)
         return np.unpackbits(bits.cpu().numpy().view(np.uint8), bitorder="little")[:nbits]
 
-    def count_errors(self, samples, first_sample=0, first_bit=0, prbs_init=1, stride=None, rx_filter=None, dfe=None):
+    def count_errors(self, samples, first_sample=0, first_bit=0, prbs_init=1, stride=None, rx_filter=None, dfe=None, mlse=None):
         """Slice, then count the positions that differ from PRBS-k (started `first_bit` bits after `prbs_init`)."""
-        bits, nbits = self.slice(samples, first_sample, stride, rx_filter=rx_filter, dfe=dfe)
+        bits, nbits = self.slice(samples, first_sample, stride, rx_filter=rx_filter, dfe=dfe, mlse=mlse)
         return self.prbsdet.count_errors(bits, nbits, first_bit=first_bit, init=prbs_init), nbits
 
     def detect(self, samples, first_sample=0, stride=None, want_err=False, want_reload=False, rx_filter=None, error_stats=None,
-               dfe=None):
+               dfe=None, mlse=None):
         """Slice at this receiver's `sample_delay`, then the exact self-synchronising detector over the
         whole stream (rx.py:41-46 at scale): totals as PRBSErrorDetector.run_stream returns them.  error_stats: an
         errstat.ErrorStats that is fed the detector's errors (PRBSErrorDetector.run_stream)."""
-        bits, nbits = self.slice(samples, first_sample, stride, rx_filter=rx_filter, dfe=dfe)
+        bits, nbits = self.slice(samples, first_sample, stride, rx_filter=rx_filter, dfe=dfe, mlse=mlse)
         return self.prbsdet.run_stream(bits, nbits, want_err=want_err, want_reload=want_reload, error_stats=error_stats)
 
     def interpolate(self, samples, shift=4, out_dtype=torch.int16):

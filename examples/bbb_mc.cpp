@@ -31,6 +31,8 @@
 //                       samples per bit into the exact detector: one JSON line with both error counts
 //          dfe:         --dfe 1 [--eye-samples 1e6] [--prbs 31] [--nv 8]   the same receiver behind an echo of 0.7 one bit late
 //                       (bbb_fir_filter as the channel), without and with one feedback tap (bbb_dfe_run): errors of both
+//          mlse:        --mlse MEM [--eye-samples 1e6] [--prbs 31] [--nv 8]   the same record through the moving average, the DFE
+//                       and the Viterbi sequence detector with a target of MEM (1..4) symbols of memory (bbb_mlse_run)
 //                       from the exact detector, and the call's region counters
 //          link:        --link 1 [--eye-samples 1e6] [--prbs 31] [--nv 8] [--shape 16] [--delay 2]   the bathtub of one transmitter
 //                       setting decided on the raw sample (bbb_tx_ber_sweep_*) and behind the moving average of rx.py:24-26
@@ -206,7 +208,7 @@ int main(int argc, char **argv) {
     bool lags_set = false;
     int shape = 16, eye_shift = 4;
     double eye_samples = 1e6;
-    int tx_sweep = 0, nv_lo = 0, nv_hi = 15, fir = 0, dfe = 0, link = 0, link_delay = 2, errstat = 0, xcorr = 0, ddc = 0, nco_pm = 100;
+    int tx_sweep = 0, nv_lo = 0, nv_hi = 15, fir = 0, dfe = 0, mlse = 0, link = 0, link_delay = 2, errstat = 0, xcorr = 0, ddc = 0, nco_pm = 100;
     unsigned long errstat_guard = 64;
     unsigned long long init0 = 1;
     double bits = 1e9, from = 0, to = 10, step = 1, loopback = 0, nsamples = 0, grng_eval = 0;
@@ -254,6 +256,7 @@ int main(int argc, char **argv) {
         else if (a == "--tx-sweep") tx_sweep = std::atoi(v);
         else if (a == "--fir") fir = std::atoi(v);
         else if (a == "--dfe") dfe = std::atoi(v);
+        else if (a == "--mlse") mlse = std::atoi(v);
         else if (a == "--link") link = std::atoi(v);
         else if (a == "--delay") link_delay = std::atoi(v);
         else if (a == "--errstat") errstat = std::atoi(v);
@@ -703,8 +706,8 @@ int main(int argc, char **argv) {
     }
 
     // ---- an echo one bit late: the moving-average receiver beside the same filter with one feedback tap (bbb_dfe_run) ---------
-    if (dfe) {
-        if (eye_samples < 1 || nv < 0 || nv > 15) { std::fprintf(stderr, "--eye-samples >= 1, --nv 0..15\n"); return 2; }
+    if (dfe || mlse) {
+        if (eye_samples < 1 || nv < 0 || nv > 15 || mlse < 0 || mlse > 4) { std::fprintf(stderr, "--eye-samples >= 1, --nv 0..15, --mlse 1..4\n"); return 2; }
         bbb_tx_cfg cfg{};
         for (int i = 30; i < 34; i++) cfg.coeffs[i] = 254;          // the rectangular pulse (bitshaper.py:108)
         cfg.source = 0;
@@ -748,6 +751,18 @@ int main(int argc, char **argv) {
         dc.fb[0] = 4 * 111;
         CHECK(bbb_dfe_run(y, ntx, 0, &dc, state, b, nullptr, stats, &ndfe, 0, nullptr));
         CHECK(bbb_prbs_detector_stream(k, b, ndfe, nullptr, nullptr, &eq, 0, 0, 0, nullptr));
+        // the sequence detector on the same filter: the bit and its echo are the target, 4 * 158 and 4 * 111 in units of y
+        uint64_t nml = 0;
+        bbb_detector_stats ml{};
+        if (mlse) {
+            bbb_mlse_cfg mc{};
+            mc.ff = dc.ff;
+            mc.mem = (uint32_t)mlse;
+            mc.g[0] = 4 * 158;
+            mc.g[1] = 4 * 111;
+            CHECK(bbb_mlse_run(y, ntx, 0, 0, 1, &mc, b, nullptr, &nml, 0, nullptr));
+            CHECK(bbb_prbs_detector_stream(k, b, nml, nullptr, nullptr, &ml, 0, 0, 0, nullptr));
+        }
         const double secs = now_s() - t0;
         uint64_t st[4] = {0, 0, 0, 0};
         if (hipMemcpy(st, stats, sizeof st, hipMemcpyDeviceToHost) != hipSuccess) { std::fprintf(stderr, "copy failed\n"); return 1; }
@@ -757,6 +772,14 @@ int main(int argc, char **argv) {
         (void)hipFree(b);
         (void)hipFree(stats);
         (void)hipFree(state);
+        if (mlse) {
+            std::printf("{\"mode\": \"mlse\", \"samples\": %llu, \"prbs\": %d, \"nv\": %d, \"echo\": 0.7, \"moving_average\": {\"bits\": %llu, \"errors\": %llu}, "
+                        "\"dfe\": {\"fb\": %d, \"bits\": %llu, \"errors\": %llu}, \"mlse\": {\"mem\": %d, \"g\": [%d, %d], \"bits\": %llu, \"errors\": %llu}, "
+                        "\"seconds\": %.4f}\n", (unsigned long long)ntx, k, nv, (unsigned long long)lin.bits, (unsigned long long)lin.errors, dc.fb[0],
+                        (unsigned long long)eq.bits, (unsigned long long)eq.errors, mlse, 4 * 158, 4 * 111, (unsigned long long)ml.bits,
+                        (unsigned long long)ml.errors, secs);
+            return 0;
+        }
         std::printf("{\"mode\": \"dfe\", \"samples\": %llu, \"prbs\": %d, \"nv\": %d, \"echo\": 0.7, \"moving_average\": {\"bits\": %llu, \"errors\": %llu}, "
                     "\"dfe\": {\"fb\": %d, \"bits\": %llu, \"errors\": %llu, \"regions\": %llu, \"not_proven\": %llu, \"repaired\": %llu}, "
                     "\"seconds\": %.4f}\n", (unsigned long long)ntx, k, nv, (unsigned long long)lin.bits, (unsigned long long)lin.errors, dc.fb[0],

@@ -767,6 +767,63 @@ int bbb_dfe_geometry(uint32_t decim, uint64_t *step_samples, uint64_t *step_symb
 int bbb_dfe_model_host(const int16_t *in, uint64_t nin, uint32_t nbefore, const bbb_dfe_cfg *cfg, uint32_t *state,
                        uint64_t *bits_packed, void *soft, uint64_t *nbits_out);
 
+/* ---- Viterbi sequence detector (MLSE): feed-forward FIR, a target of up to 4 symbols of memory, exact -------------------- */
+
+/* The receiver's strongest detector: the most likely SEQUENCE of bits behind a channel with inter-symbol interference,
+ * where the DFE decides bit by bit and propagates its errors.  All integers.  ff is a bbb_fir_cfg under its own rules
+ * (decim = samples per bit, phase = sampling phase, history by nbefore), mem = L is 1..BBB_MLSE_MAX_MEM, g[0..L] the target
+ * taps in units of y, NS = 2^L:
+ *   y[k]      = sat16(acc(phase + k * decim) >> ff.shift)      what bbb_fir_filter writes as int16; k counted from the call
+ *   K         = first_symbol + k                               the absolute symbol number
+ *   state h   : L bits, bit i = the decision of symbol K - 1 - i (the DFE's convention)
+ *   s(h, b)   = g[0] d(b) + sum_{i = 1..L} g[i] d(bit i - 1 of h)        d(1) = +1, d(0) = -1
+ *   gain(h,b) = 2 y s(h, b) - s(h, b)^2                        maximised: -(y - s)^2 with y^2 dropped
+ *   h'        = ((h << 1) | b) & (NS - 1)
+ * ACS: the predecessors of h' are h = (h' >> 1) | (c << (L - 1)), c = 0, 1; the larger m[h] + gain(h, h' & 1) survives, a tie
+ * goes to c = 0.
+ * Blocks on ABSOLUTE symbol numbers: block j is the symbols [j B, (j + 1) B); its bits come from ONE Viterbi run over the
+ * window [max(0, j B - W), min(Nend, (j + 1) B + D)).  A window that starts at symbol 0 allows init_state (masked to L bits)
+ * alone, any other window starts every state at metric 0.  At the window's end the largest metric is the best state, on a
+ * tie the lowest index; the path is traced back along the survivors, the decision of symbol K is bit 0 of the path's state
+ * behind symbol K, and only the block's own symbols are emitted.  B = block_symbols, W = warmup_symbols and D =
+ * lookahead_symbols (0: 192, 32, 32) ARE part of the definition; 1 <= B, W <= 128, D <= 128, B + W + D <= 512.  Nend is the
+ * record's end, known only to a call with final != 0: Nend = first_symbol + nsym, and such a call decides all its nsym
+ * symbols.  A call with final == 0 decides the symbols below the largest block boundary E with E + D <= first_symbol + nsym:
+ * the whole blocks whose unclipped window lies inside it.  first_symbol may sit anywhere inside a block: the block's window
+ * is the same absolute one, its symbols in front of the call are read through nbefore (and are 0-filled beyond it, the FIR's
+ * rule).  So a capture cut at block boundaries E, each piece with its history, gives the bits of one call; the detector has
+ * no state on the device.
+ * sum |g[i]| <= 2^20: with |y| <= 32768 and at most 512 symbols every path metric stays below 2^50, int64 is exact. */
+#define BBB_MLSE_MAX_MEM 4
+typedef struct {
+    bbb_fir_cfg ff;             /* out_bytes must be valid and is otherwise ignored: y is the int16 form */
+    uint32_t mem;               /* 1..4 */
+    int32_t  g[5];              /* g[0]: the cursor, g[i]: the symbol i back; entries beyond mem are ignored */
+    uint32_t init_state;        /* the decisions in front of symbol 0, bit i = symbol -1 - i */
+    uint32_t block_symbols, warmup_symbols, lookahead_symbols;      /* 0: the default */
+} bbb_mlse_cfg;
+
+/* The sizes of a call, from sizes alone (host only, works without a GPU; the three outputs may be NULL): *nsym = nout of
+ * ff, *ndecided as above, *nbefore_wanted the history in samples with which the call's first window is not zero-filled:
+ * (first_symbol - the window's first symbol) * decim + ntaps - 1 less the `phase` samples the call itself holds; at a block
+ * boundary that is min(first_symbol, W) * decim + ntaps - 1 - phase.  BBB_EINVAL for everything wrong with cfg and for
+ * first_symbol + nsym > 2^58. */
+int bbb_mlse_plan(const bbb_mlse_cfg *cfg, uint64_t nin, uint64_t first_symbol, int final, uint64_t *nsym, uint64_t *ndecided,
+                  uint64_t *nbefore_wanted);
+/* bits_packed_dev: the decision of symbol first_symbol + k is bit k, LSB first in u64 words, the layout of bbb_fir_slice,
+ * the unused bits of the last word 0 (ceil(ndecided / 64) words, 8-byte aligned; words beyond them are not touched).
+ * stats_dev (may be NULL): uint64[2] on the device, ADDED TO: windows walked, symbols decided.  *ndecided_out (host, may be
+ * NULL) receives ndecided, which is bbb_mlse_plan's.  in_dev as in bbb_fir_filter; of nbefore only what the first window
+ * reaches (nbefore_wanted) is read.  BBB_EINVAL before the device is touched: everything wrong with cfg (ff's own rules,
+ * mem, sum |g|, the geometry), nulls, misaligned pointers, an output that overlaps the samples read, first_symbol + nsym >
+ * 2^58.  nin = 0 or ndecided = 0 writes nothing.  Asynchronous on hip_stream; a device without gfx950 gives BBB_ENODEV. */
+int bbb_mlse_run(const int16_t *in_dev, uint64_t nin, uint32_t nbefore, uint64_t first_symbol, int final, const bbb_mlse_cfg *cfg,
+                 uint64_t *bits_packed_dev, uint64_t *stats_dev, uint64_t *ndecided_out, int device, void *hip_stream);
+/* The definition as a plain serial loop over host memory (works without a GPU): in[-1] .. in[-nbefore] readable,
+ * bits_packed / *ndecided_out as in bbb_mlse_run. */
+int bbb_mlse_model_host(const int16_t *in, uint64_t nin, uint32_t nbefore, uint64_t first_symbol, int final, const bbb_mlse_cfg *cfg,
+                        uint64_t *bits_packed, uint64_t *ndecided_out);
+
 /* ---- the filtered link: eye, bathtub and BER sweep behind a receive filter (rx.py:24-26) -------------------------------- */
 
 /* What bbb_tx_eye_run and bbb_tx_ber_sweep_run give for the raw sample, for the sample AFTER the receive filter, the
