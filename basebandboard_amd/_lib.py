@@ -29,6 +29,7 @@ SYMBOLS = [
     "bbb_ddc_run", "bbb_ddc_polar_host",
     "bbb_dfe_run", "bbb_dfe_geometry", "bbb_dfe_model_host",
     "bbb_mlse_plan", "bbb_mlse_run", "bbb_mlse_model_host",
+    "bbb_timing_plan", "bbb_timing_run", "bbb_timing_model_host",
 ]
 
 
@@ -115,6 +116,12 @@ class MlseCfg(C.Structure):
     """bbb_mlse_cfg"""
     _fields_ = [("ff", FirCfg), ("mem", C.c_uint32), ("g", C.c_int32 * 5), ("init_state", C.c_uint32),
                 ("block_symbols", C.c_uint32), ("warmup_symbols", C.c_uint32), ("lookahead_symbols", C.c_uint32)]
+
+
+class TimingCfg(C.Structure):
+    """bbb_timing_cfg"""
+    _fields_ = [("ff", FirCfg), ("spb", C.c_uint32), ("block_symbols", C.c_uint32), ("hysteresis_shift", C.c_uint32),
+                ("threshold", C.c_int32), ("strict", C.c_uint32), ("init_phase", C.c_uint32), ("chunk_blocks", C.c_uint32)]
 
 
 class DdcCfg(C.Structure):
@@ -283,6 +290,9 @@ def lib():
     l.bbb_mlse_plan.argtypes = [C.POINTER(MlseCfg), u64, u64, i32, u64p, u64p, u64p]
     l.bbb_mlse_run.argtypes = [vp, u64, C.c_uint32, u64, i32, C.POINTER(MlseCfg), vp, vp, u64p, i32, vp]
     l.bbb_mlse_model_host.argtypes = [vp, u64, C.c_uint32, u64, i32, C.POINTER(MlseCfg), vp, u64p]
+    l.bbb_timing_plan.argtypes = [C.POINTER(TimingCfg), u64, i32, u64p, u64p, u64p, u64p]
+    l.bbb_timing_run.argtypes = [vp, u64, C.c_uint32, i32, C.POINTER(TimingCfg), vp, vp, vp, vp, vp, vp, i32, vp]
+    l.bbb_timing_model_host.argtypes = [vp, u64, C.c_uint32, i32, C.POINTER(TimingCfg), vp, vp, vp, vp, vp, u64p]
     u8p = C.POINTER(C.c_uint8)
     l.bbb_gf2_berlekamp_massey.argtypes = [u8p, u64, u8p, C.POINTER(C.c_int64)]
     l.bbb_gf2_recur.argtypes = [i32, i32, u64p, u8p, i32, u8p]

@@ -33,6 +33,9 @@
 //                       (bbb_fir_filter as the channel), without and with one feedback tap (bbb_dfe_run): errors of both
 //          mlse:        --mlse MEM [--eye-samples 1e6] [--prbs 31] [--nv 8]   the same record through the moving average, the DFE
 //                       and the Viterbi sequence detector with a target of MEM (1..4) symbols of memory (bbb_mlse_run)
+//          timing:      --timing OFFSET [--eye-samples 1e6] [--prbs 31] [--nv 8]   the record of --fir resampled on the host with a
+//                       clock offset of OFFSET / 65536 (20: 305 ppm), then the moving-average slicer at its one fixed phase beside
+//                       the timing recovery (bbb_timing_run) behind the same filter: errors of both, wraps and bits emitted
 //                       from the exact detector, and the call's region counters
 //          link:        --link 1 [--eye-samples 1e6] [--prbs 31] [--nv 8] [--shape 16] [--delay 2]   the bathtub of one transmitter
 //                       setting decided on the raw sample (bbb_tx_ber_sweep_*) and behind the moving average of rx.py:24-26
@@ -208,7 +211,7 @@ int main(int argc, char **argv) {
     bool lags_set = false;
     int shape = 16, eye_shift = 4;
     double eye_samples = 1e6;
-    int tx_sweep = 0, nv_lo = 0, nv_hi = 15, fir = 0, dfe = 0, mlse = 0, link = 0, link_delay = 2, errstat = 0, xcorr = 0, ddc = 0, nco_pm = 100;
+    int tx_sweep = 0, nv_lo = 0, nv_hi = 15, fir = 0, dfe = 0, mlse = 0, timing = 0, link = 0, link_delay = 2, errstat = 0, xcorr = 0, ddc = 0, nco_pm = 100;
     unsigned long errstat_guard = 64;
     unsigned long long init0 = 1;
     double bits = 1e9, from = 0, to = 10, step = 1, loopback = 0, nsamples = 0, grng_eval = 0;
@@ -257,6 +260,7 @@ int main(int argc, char **argv) {
         else if (a == "--fir") fir = std::atoi(v);
         else if (a == "--dfe") dfe = std::atoi(v);
         else if (a == "--mlse") mlse = std::atoi(v);
+        else if (a == "--timing") timing = std::atoi(v);
         else if (a == "--link") link = std::atoi(v);
         else if (a == "--delay") link_delay = std::atoi(v);
         else if (a == "--errstat") errstat = std::atoi(v);
@@ -702,6 +706,77 @@ int main(int argc, char **argv) {
                     "\"seconds\": %.4f}\n", (unsigned long long)ntx, k, nv, (unsigned long long)plain.bits, (unsigned long long)plain.errors,
                     (unsigned long long)plain.reload_clocks, (unsigned long long)filt.bits, (unsigned long long)filt.errors,
                     (unsigned long long)filt.reload_clocks, secs);
+        return 0;
+    }
+
+    // ---- a capture from an ADC with its own clock: one fixed phase beside the timing recovery (bbb_timing_run) -----------------
+    if (timing) {
+        if (eye_samples < 4096 || nv < 0 || nv > 15 || timing < -1000 || timing > 1000) {
+            std::fprintf(stderr, "--eye-samples >= 4096, --nv 0..15, --timing -1000..1000 (not 0)\n");
+            return 2;
+        }
+        bbb_tx_cfg cfg{};
+        for (int i = 30; i < 34; i++) cfg.coeffs[i] = 254;          // the rectangular pulse (bitshaper.py:108)
+        cfg.source = 0;
+        cfg.prbs_k = k;
+        cfg.prbs_state = 1;
+        cfg.bit_en = 1;
+        cfg.noise_en = 1;
+        cfg.noise_var = nv;
+        cfg.warmup = 16;
+        const uint64_t init[8] = {init0, 0, 0, 0, 0, 0, 0, 0};
+        bbb_lutopt *h = nullptr;
+        CHECK(bbb_lutopt_create(&h, m.n, m.taps.data(), m.off.data(), init, 0));
+        const uint64_t ntx = (uint64_t)eye_samples;
+        // y[n] = (x[i] (65536 - f) + x[i + 1] f) >> 16 at pos = n * (65536 + OFFSET), i = pos >> 16, f = pos & 65535
+        const uint64_t step = (uint64_t)(65536 + timing);
+        const uint64_t nrx = std::min<uint64_t>(ntx, ((ntx - 2) << 16) / step);
+        bbb_timing_cfg tc{};
+        CHECK(bbb_fir_moving_average(&tc.ff, 0));
+        tc.spb = 8;
+        tc.init_phase = BBB_TIMING_ACQUIRE;
+        uint64_t nblocks = 0, nconsumed = 0, max_bits = 0;
+        CHECK(bbb_timing_plan(&tc, nrx, 1, &nblocks, &nconsumed, &max_bits, nullptr));
+        int16_t *w = nullptr;
+        uint64_t *b = nullptr, *words = nullptr;                    // words: state[2], stats[4], nbits
+        if (hipMalloc((void **)&w, ntx * sizeof(int16_t)) != hipSuccess || hipMalloc((void **)&b, (max_bits / 64 + 2) * sizeof(uint64_t)) != hipSuccess ||
+            hipMalloc((void **)&words, 7 * sizeof(uint64_t)) != hipSuccess || hipMemset(words, 0, 7 * sizeof(uint64_t)) != hipSuccess) {
+            std::fprintf(stderr, "hipMalloc failed\n");
+            return 1;
+        }
+        CHECK(bbb_tx_fill_i16(h, &cfg, w, ntx, 0));
+        std::vector<int16_t> x(ntx), y(nrx);
+        if (hipMemcpy(x.data(), w, ntx * sizeof(int16_t), hipMemcpyDeviceToHost) != hipSuccess) { std::fprintf(stderr, "copy failed\n"); return 1; }
+        for (uint64_t n = 0; n < nrx; ++n) {
+            const uint64_t pos = n * step, i = pos >> 16;
+            const int64_t f = (int64_t)(pos & 65535);
+            y[n] = (int16_t)(((int64_t)x[i] * (65536 - f) + (int64_t)x[i + 1] * f) >> 16);
+        }
+        if (hipMemcpy(w, y.data(), nrx * sizeof(int16_t), hipMemcpyHostToDevice) != hipSuccess) { std::fprintf(stderr, "copy failed\n"); return 1; }
+        uint64_t nfix = 0;
+        bbb_detector_stats fix{}, trk{};
+        const double t0 = now_s();
+        bbb_fir_cfg fc = tc.ff;
+        fc.decim = 8;
+        fc.phase = 2;                                               // where the running sum of four is complete without an offset
+        CHECK(bbb_fir_slice(w, nrx, 0, &fc, 0, 0, b, &nfix, 0, nullptr));
+        CHECK(bbb_prbs_detector_stream(k, b, nfix, nullptr, nullptr, &fix, 0, 0, 0, nullptr));
+        CHECK(bbb_timing_run(w, nrx, 0, 1, &tc, words, b, nullptr, nullptr, words + 2, words + 6, 0, nullptr));
+        uint64_t out[7];
+        if (hipMemcpy(out, words, sizeof out, hipMemcpyDeviceToHost) != hipSuccess) { std::fprintf(stderr, "copy failed\n"); return 1; }
+        CHECK(bbb_prbs_detector_stream(k, b, out[6], nullptr, nullptr, &trk, 0, 0, 0, nullptr));
+        const double secs = now_s() - t0;
+        CHECK(bbb_lutopt_destroy(h));
+        (void)hipFree(w);
+        (void)hipFree(b);
+        (void)hipFree(words);
+        std::printf("{\"mode\": \"timing\", \"samples\": %llu, \"prbs\": %d, \"nv\": %d, \"offset_ppm\": %.1f, \"fixed_phase\": {\"phase\": 2, \"bits\": %llu, "
+                    "\"errors\": %llu, \"reload_clocks\": %llu}, \"timing\": {\"bits\": %llu, \"errors\": %llu, \"reload_clocks\": %llu, \"blocks\": %llu, "
+                    "\"moves\": %llu, \"wraps_up\": %llu, \"wraps_down\": %llu, \"last_phase\": %llu}, \"seconds\": %.4f}\n",
+                    (unsigned long long)nrx, k, nv, timing / 65536.0 * 1e6, (unsigned long long)fix.bits, (unsigned long long)fix.errors,
+                    (unsigned long long)fix.reload_clocks, (unsigned long long)trk.bits, (unsigned long long)trk.errors,
+                    (unsigned long long)trk.reload_clocks, (unsigned long long)out[2], (unsigned long long)out[3], (unsigned long long)out[4],
+                    (unsigned long long)out[5], (unsigned long long)(out[0] & 0xFFFFFFFFull), secs);
         return 0;
     }
 

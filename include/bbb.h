@@ -824,6 +824,66 @@ int bbb_mlse_run(const int16_t *in_dev, uint64_t nin, uint32_t nbefore, uint64_t
 int bbb_mlse_model_host(const int16_t *in, uint64_t nin, uint32_t nbefore, uint64_t first_symbol, int final, const bbb_mlse_cfg *cfg,
                         uint64_t *bits_packed, uint64_t *ndecided_out);
 
+/* ---- symbol timing recovery: a block-wise early/late tracker of the sampling phase, exact whatever the data are ---------- */
+
+/* Every decision above is taken at phase + k * decim: one sampling phase for the whole record.  A capture from an ADC with
+ * its own clock drifts; this tracker follows it and hands out one decision (and soft value) per symbol.  All integers.
+ * ff is a bbb_fir_cfg under its own rules with decim == 1 and phase == 0 (one tap {1}: no filter); a(n) = acc(n) for n in
+ * [-1, nin), history by bbb_fir_filter's rule.  P = spb (3..256) samples per bit, L = block_symbols (8..1024, L * P <= 65536;
+ * 0: 64), h = hysteresis_shift (1..63; 0: 4), threshold and strict as in bbb_dfe_cfg, init_phase < P or BBB_TIMING_ACQUIRE.
+ * Block j is the samples [j L P, (j + 1) L P) inside [0, nin); nblocks = final ? ceil(nin / (L P)) : floor(nin / (L P)), so
+ * only the last block of a final call may be partial.  Its metric, for p in [0, P):
+ *   E_j[p] = sum over i in [0, L) with t = j L P + i P + p < nin of |a(t) - threshold|              int64, below 2^43
+ * The state is (locked, phi); a zeroed state is out of reset.
+ *   first block after reset: phi_j = init_phase if that is below P, else the p with the largest E_j[p] (the lowest on a
+ *                            tie); m_j = 0
+ *   every other block:       phi = phi_(j-1), cur = E_j[phi], up = E_j[(phi + 1) mod P], dn = E_j[(phi + P - 1) mod P],
+ *                            margin = cur >> h; m_j = +1 if up > cur + margin and up >= dn, else -1 if dn > cur + margin,
+ *                            else 0; phi_j = (phi + m_j) mod P
+ *   wrap:                    w_j = +1 if m_j = +1 and phi_j = 0; -1 if m_j = -1 and phi_j = P - 1; else 0
+ * Block j emits the instants t = j L P + phi_j + i P for i = w_j .. L - 1 with t < nin: L - 1 bits after a wrap up, L + 1 after
+ * a wrap down (the first of them one sample in front of the block; for block 0 that is a(-1), read through the history),
+ * L otherwise.  No bit is sampled twice or skipped; consecutive instants are P - 1, P or P + 1 samples apart.
+ * bit = a(t) >= threshold (> with strict); soft value sat16(a(t) >> ff.shift) with out_bytes 2, a(t) with out_bytes 4; both
+ * go out in order of t from bit 0 / element 0 of the call's outputs.
+ * chunk_blocks (0: the default) only places the boundaries of the device's work: no output depends on it. */
+#define BBB_TIMING_ACQUIRE 0xFFFFFFFFu
+typedef struct {
+    bbb_fir_cfg ff;            /* decim 1, phase 0; shift and out_bytes count only where soft values are asked for */
+    uint32_t spb;              /* P: 3..256 */
+    uint32_t block_symbols;    /* L: 8..1024, L * P <= 65536; 0: 64 */
+    uint32_t hysteresis_shift; /* h: 1..63; 0: 4 */
+    int32_t  threshold;
+    uint32_t strict;
+    uint32_t init_phase;       /* < P, or BBB_TIMING_ACQUIRE */
+    uint32_t chunk_blocks;     /* blocks one workgroup walks; 0: the default */
+} bbb_timing_cfg;
+
+/* The sizes of a call, from sizes alone (host only, works without a GPU; every output may be NULL): *nblocks as above,
+ * *nconsumed = min(nin, nblocks * L * P), *max_bits = nblocks * (L + 1), *nbefore_wanted = ntaps (ntaps - 1 for the filter,
+ * one for the early instant).  BBB_EINVAL for everything wrong with cfg. */
+int bbb_timing_plan(const bbb_timing_cfg *cfg, uint64_t nin, int final, uint64_t *nblocks, uint64_t *nconsumed, uint64_t *max_bits,
+                    uint64_t *nbefore_wanted);
+/* state_dev: uint64[2] on the device, read at the start and written at the end: [0] bit 63 is `locked`, the low bits are
+ * phi of the last block; [1] the bits emitted since reset (added to).  A record cut at multiples of L P, each piece with
+ * ntaps samples of history and these words, `final` on the last piece only, gives the bits, soft values, phases and state
+ * of one call.  bits_packed_dev: LSB first in u64 words, all ceil(max_bits / 64) words are written, the bits from nbits on
+ * are 0.  soft_dev (may be NULL): room for max_bits elements, nbits of them written.  phase_dev (may be NULL):
+ * uint8[nblocks], phi_j.  stats_dev (may be NULL): uint64[4], ADDED TO: blocks, moves, wraps up, wraps down.  nbits_dev:
+ * one uint64 on the device, written: the count depends on the data, so the host learns it by reading this.  nblocks == 0
+ * only rewrites the state; a call that is not final ignores the samples beyond nconsumed.  in_dev as in bbb_fir_filter, of
+ * nbefore the nearest ntaps are used.  BBB_EINVAL before the device is touched: everything wrong with cfg (ff's own rules,
+ * decim != 1, the ranges above), nulls, misaligned pointers, outputs that overlap the samples read or each other.  The
+ * call's scratch (P + 10 bytes per block and some per chunk) comes from the device's memory pool on hip_stream; there is no
+ * host round trip inside the call.  Asynchronous; a device without gfx950 gives BBB_ENODEV. */
+int bbb_timing_run(const int16_t *in_dev, uint64_t nin, uint32_t nbefore, int final, const bbb_timing_cfg *cfg, uint64_t *state_dev,
+                   uint64_t *bits_packed_dev, void *soft_dev, uint8_t *phase_dev, uint64_t *stats_dev, uint64_t *nbits_dev, int device,
+                   void *hip_stream);
+/* The definition as a plain serial loop over host memory (works without a GPU): in[-1] .. in[-nbefore] readable, state[2],
+ * bits_packed / soft / phase / stats as in bbb_timing_run, *nbits_out (may be NULL) the bits emitted. */
+int bbb_timing_model_host(const int16_t *in, uint64_t nin, uint32_t nbefore, int final, const bbb_timing_cfg *cfg, uint64_t *state,
+                          uint64_t *bits_packed, void *soft, uint8_t *phase, uint64_t *stats, uint64_t *nbits_out);
+
 /* ---- the filtered link: eye, bathtub and BER sweep behind a receive filter (rx.py:24-26) -------------------------------- */
 
 /* What bbb_tx_eye_run and bbb_tx_ber_sweep_run give for the raw sample, for the sample AFTER the receive filter, the
