@@ -30,6 +30,7 @@ SYMBOLS = [
     "bbb_dfe_run", "bbb_dfe_geometry", "bbb_dfe_model_host",
     "bbb_mlse_plan", "bbb_mlse_run", "bbb_mlse_model_host",
     "bbb_timing_plan", "bbb_timing_run", "bbb_timing_model_host",
+    "bbb_conv_plan", "bbb_conv_encode", "bbb_conv_encode_host", "bbb_conv_decode", "bbb_conv_model_host",
 ]
 
 
@@ -122,6 +123,16 @@ class TimingCfg(C.Structure):
     """bbb_timing_cfg"""
     _fields_ = [("ff", FirCfg), ("spb", C.c_uint32), ("block_symbols", C.c_uint32), ("hysteresis_shift", C.c_uint32),
                 ("threshold", C.c_int32), ("strict", C.c_uint32), ("init_phase", C.c_uint32), ("chunk_blocks", C.c_uint32)]
+
+
+CONV_SOFT16, CONV_HARD = 0, 1
+
+
+class ConvCfg(C.Structure):
+    """bbb_conv_cfg"""
+    _fields_ = [("K", C.c_uint32), ("n", C.c_uint32), ("gen", C.c_uint32 * 3), ("init_state", C.c_uint32), ("period", C.c_uint32),
+                ("keep", C.c_uint32 * 3), ("terminated", C.c_uint32), ("block_steps", C.c_uint32), ("warmup_steps", C.c_uint32),
+                ("lookahead_steps", C.c_uint32)]
 
 
 class DdcCfg(C.Structure):
@@ -293,6 +304,11 @@ def lib():
     l.bbb_timing_plan.argtypes = [C.POINTER(TimingCfg), u64, i32, u64p, u64p, u64p, u64p]
     l.bbb_timing_run.argtypes = [vp, u64, C.c_uint32, i32, C.POINTER(TimingCfg), vp, vp, vp, vp, vp, vp, i32, vp]
     l.bbb_timing_model_host.argtypes = [vp, u64, C.c_uint32, i32, C.POINTER(TimingCfg), vp, vp, vp, vp, vp, u64p]
+    l.bbb_conv_plan.argtypes = [C.POINTER(ConvCfg), u64, u64, i32, u64p, u64p, u64p]
+    l.bbb_conv_encode.argtypes = [vp, u64, u64, C.POINTER(ConvCfg), vp, vp, u64p, i32, vp]
+    l.bbb_conv_encode_host.argtypes = [vp, u64, u64, C.POINTER(ConvCfg), C.POINTER(C.c_uint32), vp, u64p]
+    l.bbb_conv_decode.argtypes = [vp, u64, u64, u64, u64, i32, i32, C.POINTER(ConvCfg), vp, vp, u64p, i32, vp]
+    l.bbb_conv_model_host.argtypes = [vp, u64, u64, u64, u64, i32, i32, C.POINTER(ConvCfg), vp, u64p]
     u8p = C.POINTER(C.c_uint8)
     l.bbb_gf2_berlekamp_massey.argtypes = [u8p, u64, u8p, C.POINTER(C.c_int64)]
     l.bbb_gf2_recur.argtypes = [i32, i32, u64p, u8p, i32, u8p]

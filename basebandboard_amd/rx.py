@@ -30,7 +30,7 @@ class RX:
         self.prbs_k, self.samples_per_bit, self.sample_delay, self.device = prbs_k, int(samples_per_bit), int(sample_delay), int(device)
         self.prbsdet = PRBSErrorDetector(prbs_k, device=device)
 
-    def slice(self, samples, first_sample=0, stride=None, strict=False, rx_filter=None, dfe=None, mlse=None, timing=None):
+    def slice(self, samples, first_sample=0, stride=None, strict=False, rx_filter=None, dfe=None, mlse=None, timing=None, fec=None):
         """Decided bits of an int16 CUDA tensor: bit j = samples[first_sample + sample_delay + j*stride] >= 0
         (`strict`: > 0, the capture script software/memdump/decode.py:15).  Returns (packed int64 tensor, nbits).
         rx_filter (a fir.FIR): the same indices of the filtered stream instead, acc(..) >= 0 (bbb_fir_slice; the
@@ -41,7 +41,13 @@ class RX:
         symbol 0); the stride is its spb.  It excludes dfe and rx_filter.
         timing (a timing.TimingRecovery, out of reset): the decisions at the instants its tracker chooses instead
         (bbb_timing_run, one final call).  The record starts at first_sample; sample_delay is IGNORED, the tracker finds the
-        phase itself.  It carries its own filter, threshold and strictness and excludes rx_filter, dfe, mlse and stride."""
+        phase itself.  It carries its own filter, threshold and strictness and excludes rx_filter, dfe, mlse and stride.
+        fec (a fec.ConvCode): the HARD decisions of whichever path was chosen are received bits of its code, from step 0 on, and
+        are decoded in one final call (bbb_conv_decode): the decoded bits and their count come back instead.  Soft decoding
+        goes through ConvCode.decode on the int16 values of FIR.filter, DFE.equalize or TimingRecovery.recover."""
+        if fec is not None:
+            bits, nbits = self.slice(samples, first_sample, stride, strict, rx_filter, dfe, mlse, timing)
+            return fec.decode(bits, hard=True, nbits=nbits)
         if timing is not None:
             if rx_filter is not None or dfe is not None or mlse is not None or stride is not None:
                 raise ValueError("timing chooses its own instants behind its own filter: it excludes rx_filter, dfe, mlse and stride")
@@ -105,17 +111,19 @@ class RX:
         return np.unpackbits(bits.cpu().numpy().view(np.uint8), bitorder="little")[:nbits]
 
     def count_errors(self, samples, first_sample=0, first_bit=0, prbs_init=1, stride=None, rx_filter=None, dfe=None, mlse=None,
-                     timing=None):
-        """Slice, then count the positions that differ from PRBS-k (started `first_bit` bits after `prbs_init`)."""
-        bits, nbits = self.slice(samples, first_sample, stride, rx_filter=rx_filter, dfe=dfe, mlse=mlse, timing=timing)
+                     timing=None, fec=None):
+        """Slice, then count the positions that differ from PRBS-k (started `first_bit` bits after `prbs_init`).  fec: the
+        decisions are decoded first (`slice`), and the DECODED bits are counted: the coded BER."""
+        bits, nbits = self.slice(samples, first_sample, stride, rx_filter=rx_filter, dfe=dfe, mlse=mlse, timing=timing, fec=fec)
         return self.prbsdet.count_errors(bits, nbits, first_bit=first_bit, init=prbs_init), nbits
 
     def detect(self, samples, first_sample=0, stride=None, want_err=False, want_reload=False, rx_filter=None, error_stats=None,
-               dfe=None, mlse=None, timing=None):
+               dfe=None, mlse=None, timing=None, fec=None):
         """Slice at this receiver's `sample_delay`, then the exact self-synchronising detector over the
         whole stream (rx.py:41-46 at scale): totals as PRBSErrorDetector.run_stream returns them.  error_stats: an
-        errstat.ErrorStats that is fed the detector's errors (PRBSErrorDetector.run_stream)."""
-        bits, nbits = self.slice(samples, first_sample, stride, rx_filter=rx_filter, dfe=dfe, mlse=mlse, timing=timing)
+        errstat.ErrorStats that is fed the detector's errors (PRBSErrorDetector.run_stream).  fec: the decisions are decoded
+        first (`slice`), the detector runs over the decoded bits."""
+        bits, nbits = self.slice(samples, first_sample, stride, rx_filter=rx_filter, dfe=dfe, mlse=mlse, timing=timing, fec=fec)
         return self.prbsdet.run_stream(bits, nbits, want_err=want_err, want_reload=want_reload, error_stats=error_stats)
 
     def interpolate(self, samples, shift=4, out_dtype=torch.int16):

@@ -37,6 +37,11 @@
 //                       clock offset of OFFSET / 65536 (20: 305 ppm), then the moving-average slicer at its one fixed phase beside
 //                       the timing recovery (bbb_timing_run) behind the same filter: errors of both, wraps and bits emitted
 //                       from the exact detector, and the call's region counters
+//          fec:         --fec P [--eye-samples 1e6] [--prbs 31] [--nv 8]   forward error correction (bbb_conv_*): eye-samples PRBS bits
+//                       through the K = 7 code (0171, 0133), P = 1: rate 1/2, P = 2, 3, 5, 7: punctured to 2/3, 3/4, 5/6, 7/8,
+//                       sent as +-64 plus Gaussian noise of sigma 5 nv made on the host, sliced (bbb_rx_slice) and decoded
+//                       from the hard decisions and from the soft values: one JSON line with the channel's errors and both
+//                       decoders' (sigma 40 of the default nv is past what hard decisions survive at rate 3/4; --nv 5 is not)
 //          link:        --link 1 [--eye-samples 1e6] [--prbs 31] [--nv 8] [--shape 16] [--delay 2]   the bathtub of one transmitter
 //                       setting decided on the raw sample (bbb_tx_ber_sweep_*) and behind the moving average of rx.py:24-26
 //                       (bbb_link_sweep_* with the taps of bbb_fir_moving_average, the filtered stream re-timed by `delay`), the
@@ -88,6 +93,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <random>
 #include <string>
 #include <thread>
 #include <vector>
@@ -211,7 +217,7 @@ int main(int argc, char **argv) {
     bool lags_set = false;
     int shape = 16, eye_shift = 4;
     double eye_samples = 1e6;
-    int tx_sweep = 0, nv_lo = 0, nv_hi = 15, fir = 0, dfe = 0, mlse = 0, timing = 0, link = 0, link_delay = 2, errstat = 0, xcorr = 0, ddc = 0, nco_pm = 100;
+    int tx_sweep = 0, nv_lo = 0, nv_hi = 15, fir = 0, dfe = 0, mlse = 0, timing = 0, fec = 0, link = 0, link_delay = 2, errstat = 0, xcorr = 0, ddc = 0, nco_pm = 100;
     unsigned long errstat_guard = 64;
     unsigned long long init0 = 1;
     double bits = 1e9, from = 0, to = 10, step = 1, loopback = 0, nsamples = 0, grng_eval = 0;
@@ -261,6 +267,7 @@ int main(int argc, char **argv) {
         else if (a == "--dfe") dfe = std::atoi(v);
         else if (a == "--mlse") mlse = std::atoi(v);
         else if (a == "--timing") timing = std::atoi(v);
+        else if (a == "--fec") fec = std::atoi(v);
         else if (a == "--link") link = std::atoi(v);
         else if (a == "--delay") link_delay = std::atoi(v);
         else if (a == "--errstat") errstat = std::atoi(v);
@@ -706,6 +713,58 @@ int main(int argc, char **argv) {
                     "\"seconds\": %.4f}\n", (unsigned long long)ntx, k, nv, (unsigned long long)plain.bits, (unsigned long long)plain.errors,
                     (unsigned long long)plain.reload_clocks, (unsigned long long)filt.bits, (unsigned long long)filt.errors,
                     (unsigned long long)filt.reload_clocks, secs);
+        return 0;
+    }
+
+    // ---- forward error correction: the K = 7 code around a noisy two-level link, hard against soft decisions (bbb_conv_*) --------
+    if (fec) {
+        static const uint32_t keeps[8][2] = {{0, 0}, {1, 1}, {1, 3}, {5, 3}, {0, 0}, {21, 11}, {0, 0}, {81, 47}};
+        if (eye_samples < 1 || nv < 0 || nv > 15 || fec > 7 || fec < 0 || !keeps[fec][0]) {
+            std::fprintf(stderr, "--eye-samples >= 1, --nv 0..15, --fec 1, 2, 3, 5 or 7\n");
+            return 2;
+        }
+        bbb_conv_cfg cc{};
+        cc.K = 7, cc.n = 2, cc.gen[0] = 0171, cc.gen[1] = 0133;
+        cc.period = (uint32_t)fec, cc.keep[0] = keeps[fec][0], cc.keep[1] = keeps[fec][1];
+        const uint64_t nbits = (uint64_t)eye_samples;
+        uint64_t ntx = 0;
+        uint64_t *data = nullptr, *tx = nullptr, *hard = nullptr, *dec = nullptr;
+        int16_t *soft = nullptr;
+        const uint64_t max_tx = 2 * nbits;
+        if (hipMalloc((void **)&data, (nbits / 64 + 1) * 8) != hipSuccess || hipMalloc((void **)&tx, (max_tx / 64 + 1) * 8) != hipSuccess ||
+            hipMalloc((void **)&hard, (max_tx / 64 + 1) * 8) != hipSuccess || hipMalloc((void **)&dec, (nbits / 64 + 1) * 8) != hipSuccess ||
+            hipMalloc((void **)&soft, max_tx * sizeof(int16_t)) != hipSuccess) {
+            std::fprintf(stderr, "hipMalloc failed\n");
+            return 1;
+        }
+        CHECK(bbb_prbs_fill(k, 1, 0, nbits, data, 0, nullptr));
+        const double t0 = now_s();
+        CHECK(bbb_conv_encode(data, nbits, 0, &cc, nullptr, tx, &ntx, 0, nullptr));
+        std::vector<uint64_t> txh((size_t)(ntx + 63) / 64);
+        if (hipMemcpy(txh.data(), tx, txh.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) { std::fprintf(stderr, "copy failed\n"); return 1; }
+        std::vector<int16_t> x((size_t)ntx);
+        std::mt19937_64 gen(26);
+        std::normal_distribution<double> noise(0.0, 5.0 * nv);
+        for (uint64_t i = 0; i < ntx; ++i) x[(size_t)i] = (int16_t)((txh[(size_t)(i >> 6)] >> (i & 63) & 1 ? 64 : -64) + std::lrint(noise(gen)));
+        if (hipMemcpy(soft, x.data(), ntx * sizeof(int16_t), hipMemcpyHostToDevice) != hipSuccess) { std::fprintf(stderr, "copy failed\n"); return 1; }
+        uint64_t nhard = 0, nd_hard = 0, nd_soft = 0, e_hard = 0, e_soft = 0, e_channel = 0;
+        CHECK(bbb_rx_slice(soft, ntx, 1, 0, 0, hard, &nhard, 0, nullptr));
+        CHECK(bbb_conv_decode(hard, 0, nhard, 0, 0, 1, BBB_CONV_HARD, &cc, dec, nullptr, &nd_hard, 0, nullptr));
+        CHECK(bbb_prbs_check(k, 1, 0, nd_hard, dec, &e_hard, 0, nullptr));
+        CHECK(bbb_conv_decode(soft, 0, ntx, 0, 0, 1, BBB_CONV_SOFT16, &cc, dec, nullptr, &nd_soft, 0, nullptr));
+        CHECK(bbb_prbs_check(k, 1, 0, nd_soft, dec, &e_soft, 0, nullptr));
+        const double secs = now_s() - t0;
+        for (uint64_t i = 0; i < ntx; ++i) e_channel += (uint64_t)((x[(size_t)i] >= 0) != (bool)(txh[(size_t)(i >> 6)] >> (i & 63) & 1));
+        (void)hipFree(data);
+        (void)hipFree(tx);
+        (void)hipFree(hard);
+        (void)hipFree(dec);
+        (void)hipFree(soft);
+        std::printf("{\"mode\": \"fec\", \"bits\": %llu, \"prbs\": %d, \"gen\": [\"0171\", \"0133\"], \"period\": %d, \"keep\": [%u, %u], \"sigma\": %d, "
+                    "\"coded_bits\": %llu, \"channel_errors\": %llu, \"hard\": {\"bits\": %llu, \"errors\": %llu}, \"soft\": {\"bits\": %llu, \"errors\": %llu}, "
+                    "\"seconds\": %.4f}\n", (unsigned long long)nbits, k, fec, cc.keep[0], cc.keep[1], 5 * nv, (unsigned long long)ntx,
+                    (unsigned long long)e_channel, (unsigned long long)nd_hard, (unsigned long long)e_hard, (unsigned long long)nd_soft,
+                    (unsigned long long)e_soft, secs);
         return 0;
     }
 

@@ -884,6 +884,85 @@ int bbb_timing_run(const int16_t *in_dev, uint64_t nin, uint32_t nbefore, int fi
 int bbb_timing_model_host(const int16_t *in, uint64_t nin, uint32_t nbefore, int final, const bbb_timing_cfg *cfg, uint64_t *state,
                           uint64_t *bits_packed, void *soft, uint8_t *phase, uint64_t *stats, uint64_t *nbits_out);
 
+/* ---- convolutional codec: encoder, puncturing, Viterbi decoder over soft or hard decisions, exact ---------------------- */
+
+/* Forward error correction for the receiver's decisions: a rate 1/n convolutional code of constraint length K, punctured or
+ * not, encoded on the device and decoded by a Viterbi run per block.  All integers.
+ *   K 3..7, NS = 2^(K-1) states, n 2..3 coded bits per step; gen[i] nonzero and < 2^K in the CONVENTIONAL notation: bit K-1
+ *   of gen[i] weighs the current input bit, bit 0 the oldest, so (0171, 0133) and (7, 5) are written as in the books.
+ *   state h   : K-1 bits, bit i = the input bit i + 1 steps back (the DFE's and the MLSE's convention)
+ *   r         = (h << 1) | b                                   b the step's input bit
+ *   c_i       = parity of the bits j of r for which bit K-1-j of gen[i] is set          coded bit i of the step, i < n
+ *   h'        = ((h << 1) | b) & (NS - 1)                      step 0 starts from init_state (masked to K-1 bits)
+ * Puncturing: period p is 1..16; coded bit i of ABSOLUTE step t is transmitted iff bit t mod p of keep[i] is set (keep[i] <
+ * 2^p; every step keeps at least one bit, so the step count is a function of the value count).  Within a step the kept bits
+ * go out in order of i; idx(t) is the number of transmitted bits in front of step t.  The usual patterns of (0171, 0133):
+ * rate 2/3 p 2 keep {01b, 11b}; 3/4 p 3 {101b, 011b}; 5/6 p 5 {10101b, 01011b}; 7/8 p 7 {1010001b, 0101111b}.
+ * The decoder: received value number idx(t) + (kept bits below i in step t) is r_i of step t, a punctured position and a
+ * value in front of the history count as r_i = 0.
+ *   gain      = sum_{i < n} r_i d(c_i)                         d(1) = +1, d(0) = -1, maximised over the paths
+ * ACS: the predecessors of h' are h = (h' >> 1) | (c << (K-2)), c = 0, 1; the larger m[h] + gain survives, a tie goes to
+ * c = 0.  Blocks on ABSOLUTE step numbers exactly as bbb_mlse_run's: block j is the steps [j B, (j + 1) B), decided from ONE
+ * Viterbi run over [max(0, j B - W), min(Nend, (j + 1) B + D)).  A window that starts at step 0 gives init_state the metric 0
+ * and every other state -2^30, any other window starts every state at 0.  The end state is the largest metric, the lowest
+ * index on a tie; with terminated != 0 a window that ends at Nend of a final call ends in state 0 instead (the caller appended
+ * K-1 zero bits; their steps are still emitted, dropping them is the caller's business).  The decision of step t is bit 0 of
+ * the traced-back path's state behind step t.  B = block_steps, W = warmup_steps, D = lookahead_steps (0: 192, 64, 64) ARE
+ * part of the definition; 1 <= B, 1 <= W <= 128, D <= 128, B + W + D <= 512.  final and the non-final rule are bbb_mlse_run's:
+ * Nend = first_step + nsteps is known to a final call only, a call that is not final decides the steps below the largest
+ * block boundary E with E + D <= first_step + nsteps; first_step may sit anywhere.  The decoder has no state on the device.
+ * |gain| <= 3 * 32768 < 2^17 and a window is at most 512 steps: every allowed metric stays below 2^26, int32 is exact. */
+#define BBB_CONV_SOFT16 0      /* received values: int16, positive means 1, 0 is an erasure */
+#define BBB_CONV_HARD   1      /* received values: packed bits (LSB first in u64 words), a bit counts as +1 / -1 */
+typedef struct {
+    uint32_t K;                 /* 3..7 */
+    uint32_t n;                 /* 2..3 */
+    uint32_t gen[3];            /* entries beyond n are ignored */
+    uint32_t init_state;        /* the input bits in front of step 0, bit i = step -1 - i */
+    uint32_t period;            /* 1..16 */
+    uint32_t keep[3];           /* bit t mod period of keep[i]: coded bit i of step t is transmitted */
+    uint32_t terminated;        /* decoder only */
+    uint32_t block_steps, warmup_steps, lookahead_steps;           /* decoder only; 0: the default */
+} bbb_conv_cfg;
+
+/* The sizes of a decoder call, from sizes alone (host only, works without a GPU; the three outputs may be NULL): *nsteps =
+ * the largest T with idx(first_step + T) - idx(first_step) <= nin (the values of a step cut short are ignored), *ndecided
+ * as above, *nbefore_wanted the history in received values with which the call's first window is not zero-filled:
+ * idx(first_step) - idx(the window's first step).  BBB_EINVAL for everything wrong with cfg, nin > 2^60 and first_step +
+ * nsteps > 2^58. */
+int bbb_conv_plan(const bbb_conv_cfg *cfg, uint64_t nin, uint64_t first_step, int final, uint64_t *nsteps, uint64_t *ndecided,
+                  uint64_t *nbefore_wanted);
+/* The encoder: bits_dev holds the input bits of the steps [first_step, first_step + nsteps) packed LSB first in u64 words
+ * (the layout of bbb_fir_slice).  state_dev: one uint32 on the device, the state h in front of first_step, read at the
+ * start and written at the end, so a record encoded in pieces gives the bits of one call (set it to init_state in front of
+ * step 0); NULL: the state is cfg->init_state and nothing is written back.  out_dev receives the idx(first_step + nsteps) -
+ * idx(first_step) transmitted bits packed from its bit 0 on, the unused bits of the last word 0, words beyond the last
+ * untouched; *nout (host, may be NULL) the count.  nsteps = 0 writes nothing.  Termination is the caller appending K-1 zero
+ * bits.  BBB_EINVAL before the device is touched: everything wrong with cfg (the decoder's fields included), nulls,
+ * misaligned pointers, buffers that overlap, first_step + nsteps > 2^58.  Asynchronous on hip_stream; a device without
+ * gfx950 gives BBB_ENODEV. */
+int bbb_conv_encode(const uint64_t *bits_dev, uint64_t nsteps, uint64_t first_step, const bbb_conv_cfg *cfg, uint32_t *state_dev,
+                    uint64_t *out_dev, uint64_t *nout, int device, void *hip_stream);
+/* The same as a plain serial loop over host memory (works without a GPU). */
+int bbb_conv_encode_host(const uint64_t *bits, uint64_t nsteps, uint64_t first_step, const bbb_conv_cfg *cfg, uint32_t *state,
+                         uint64_t *out, uint64_t *nout);
+/* The decoder.  format: BBB_CONV_SOFT16 or BBB_CONV_HARD.  in_dev is the BASE of the received buffer (2-byte aligned int16
+ * elements, or 8-byte aligned u64 words of bits); in_first the index (element or bit) of the call's first value, which is
+ * received value idx(first_step); nin the values from there on; nbefore <= in_first values of history lie below in_first,
+ * of which only what the first window reaches (nbefore_wanted) is read.  bits_packed_dev: the decision of step first_step
+ * + k is bit k, the unused bits of the last word 0 (ceil(ndecided / 64) words, 8-byte aligned; words beyond them are not
+ * touched).  stats_dev (may be NULL): uint64[2] on the device, ADDED TO: windows walked, steps decided.  *ndecided_out
+ * (host, may be NULL) receives ndecided, which is bbb_conv_plan's.  BBB_EINVAL before the device is touched: everything
+ * wrong with cfg, an unknown format, nulls, misaligned pointers, an output that overlaps the values read or the other
+ * output, first_step + nsteps > 2^58, nin > 2^60, in_first > 2^62, nbefore > in_first.  ndecided = 0 writes nothing.
+ * Asynchronous on hip_stream; a device without gfx950 gives BBB_ENODEV. */
+int bbb_conv_decode(const void *in_dev, uint64_t in_first, uint64_t nin, uint64_t nbefore, uint64_t first_step, int final, int format,
+                    const bbb_conv_cfg *cfg, uint64_t *bits_packed_dev, uint64_t *stats_dev, uint64_t *ndecided_out, int device,
+                    void *hip_stream);
+/* The definition as a plain serial loop over host memory (works without a GPU); arguments as bbb_conv_decode's. */
+int bbb_conv_model_host(const void *in, uint64_t in_first, uint64_t nin, uint64_t nbefore, uint64_t first_step, int final, int format,
+                        const bbb_conv_cfg *cfg, uint64_t *bits_packed, uint64_t *ndecided_out);
+
 /* ---- the filtered link: eye, bathtub and BER sweep behind a receive filter (rx.py:24-26) -------------------------------- */
 
 /* What bbb_tx_eye_run and bbb_tx_ber_sweep_run give for the raw sample, for the sample AFTER the receive filter, the
