@@ -31,6 +31,7 @@ SYMBOLS = [
     "bbb_mlse_plan", "bbb_mlse_run", "bbb_mlse_model_host",
     "bbb_timing_plan", "bbb_timing_run", "bbb_timing_model_host",
     "bbb_conv_plan", "bbb_conv_encode", "bbb_conv_encode_host", "bbb_conv_decode", "bbb_conv_model_host",
+    "bbb_rs_encode", "bbb_rs_encode_host", "bbb_rs_decode", "bbb_rs_model_host",
 ]
 
 
@@ -133,6 +134,15 @@ class ConvCfg(C.Structure):
     _fields_ = [("K", C.c_uint32), ("n", C.c_uint32), ("gen", C.c_uint32 * 3), ("init_state", C.c_uint32), ("period", C.c_uint32),
                 ("keep", C.c_uint32 * 3), ("terminated", C.c_uint32), ("block_steps", C.c_uint32), ("warmup_steps", C.c_uint32),
                 ("lookahead_steps", C.c_uint32)]
+
+
+RS_NSTATS, RS_FAILED = 5, 255
+
+
+class RSCfg(C.Structure):
+    """bbb_rs_cfg"""
+    _fields_ = [("prim_poly", C.c_uint32), ("fcr", C.c_uint32), ("prim", C.c_uint32), ("nroots", C.c_uint32), ("n", C.c_uint32),
+                ("depth", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
 class DdcCfg(C.Structure):
@@ -309,6 +319,10 @@ def lib():
     l.bbb_conv_encode_host.argtypes = [vp, u64, u64, C.POINTER(ConvCfg), C.POINTER(C.c_uint32), vp, u64p]
     l.bbb_conv_decode.argtypes = [vp, u64, u64, u64, u64, i32, i32, C.POINTER(ConvCfg), vp, vp, u64p, i32, vp]
     l.bbb_conv_model_host.argtypes = [vp, u64, u64, u64, u64, i32, i32, C.POINTER(ConvCfg), vp, u64p]
+    l.bbb_rs_encode.argtypes = [vp, u64, C.POINTER(RSCfg), vp, i32, vp]
+    l.bbb_rs_encode_host.argtypes = [vp, u64, C.POINTER(RSCfg), vp]
+    l.bbb_rs_decode.argtypes = [vp, u64, C.POINTER(RSCfg), vp, vp, vp, i32, vp]
+    l.bbb_rs_model_host.argtypes = [vp, u64, C.POINTER(RSCfg), vp, vp, vp]
     u8p = C.POINTER(C.c_uint8)
     l.bbb_gf2_berlekamp_massey.argtypes = [u8p, u64, u8p, C.POINTER(C.c_int64)]
     l.bbb_gf2_recur.argtypes = [i32, i32, u64p, u8p, i32, u8p]

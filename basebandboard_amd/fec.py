@@ -14,6 +14,10 @@ get the bits of one call.  The decoder has no state on the device.
 
 Soft values are the int16 outputs of FIR.filter, DFE.equalize or TimingRecovery.recover; the decoder's zero is the decision
 threshold, so the caller SUBTRACTS THE THRESHOLD FIRST where it is not 0 (and keeps the result inside int16).
+
+A Viterbi decoder leaves its errors in bursts.  `ReedSolomon` (include/bbb.h, bbb_rs_*) is the outer code that removes them: an
+exact Reed-Solomon codec over GF(2^8) whose codewords are interleaved symbol by symbol to depth 1..8, and `Concatenated(outer,
+inner)` is the pair as one `fec=`.
 """
 import ctypes as C
 from fractions import Fraction
@@ -180,3 +184,154 @@ class ConvStream(Carry):
     def finish(self):
         """(packed bits, nbits) of the steps still held: the record ends here."""
         return self._call(torch.empty(0, dtype=torch.int16, device=torch.device("cuda", self.code.device)), True)
+
+
+def _as_bytes(name, t, device):
+    """The uint8 view of a uint8 or packed int64 CUDA tensor (byte j = bits 8j .. 8j + 7 of the packed stream)."""
+    _lib.cuda_tensor(name, t, (torch.uint8, torch.int64), "uint8 or int64", device)
+    return t if t.dtype == torch.uint8 else t.view(torch.uint8)
+
+
+class ReedSolomon:
+    """Exact Reed-Solomon codec over GF(2^8) with symbol interleaving (include/bbb.h, bbb_rs_*): the outer code that removes
+    the error bursts a Viterbi decoder leaves.  (n, k) with n <= 255 (below: shortened), t = (n - k) / 2 symbols corrected per
+    codeword; the field is `prim_poly`'s, the generator's roots alpha^(prim (fcr + i)); `depth` codewords are interleaved symbol
+    by symbol into a frame of depth * n bytes whose first depth * k bytes are the data unchanged.  The decoder is a
+    bounded-distance decoder: a codeword with more than t wrong symbols FAILS (its data pass through, nerr 255) or, rarely,
+    decodes to another codeword.  No erasures, no soft decisions, no dual basis, no frame synchronisation."""
+
+    def __init__(self, n=255, k=223, prim_poly=0x11D, fcr=0, prim=1, depth=1, device=0):
+        self.n, self.k, self.prim_poly, self.fcr, self.prim, self.depth, self.device = (int(v) for v in (n, k, prim_poly, fcr, prim, depth, device))
+        if not 1 <= self.k < self.n <= 255:
+            raise ValueError("n must be k + 1 .. 255 and k at least 1")
+        self._stats = None
+        # everything else that is wrong with the code, from the library (host only)
+        _lib.check(_lib.lib().bbb_rs_encode_host(None, 0, C.byref(self._cfg()), None), "bbb_rs_encode_host")
+
+    @classmethod
+    def ccsds(cls, depth=1, k=223, device=0):
+        """The CCSDS (255, 223) or (255, 239) code in the conventional basis at interleaving depth 1..8."""
+        if k not in (223, 239):
+            raise ValueError("the CCSDS codes are (255, 223) and (255, 239)")
+        return cls(255, k, 0x187, 112 if k == 223 else 120, 11, depth, device)
+
+    @classmethod
+    def dvb(cls, device=0):
+        """The DVB (204, 188) code: (255, 239) over 0x11D from root alpha^0, shortened."""
+        return cls(204, 188, 0x11D, 0, 1, 1, device)
+
+    @property
+    def nroots(self):
+        return self.n - self.k
+
+    @property
+    def t(self):
+        return self.nroots // 2
+
+    @property
+    def frame_bytes(self):
+        return self.depth * self.n
+
+    @property
+    def data_bytes(self):
+        return self.depth * self.k
+
+    def _cfg(self):
+        c = _lib.RSCfg()
+        c.prim_poly, c.fcr, c.prim, c.nroots, c.n, c.depth = self.prim_poly, self.fcr, self.prim, self.n - self.k, self.n, self.depth
+        return c
+
+    def _stream_ptr(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _frames(self, name, t, per):
+        b = _as_bytes(name, t, self.device)
+        if b.numel() % per:
+            raise ValueError(f"{name} must hold whole frames of {per} bytes")
+        return b, b.numel() // per
+
+    def encode(self, data):
+        """The coded frames (a uint8 CUDA tensor) of whole data frames in a uint8 or packed int64 CUDA tensor (bbb_rs_encode).
+        Asynchronous on the current torch stream."""
+        b, nf = self._frames("data", data, self.data_bytes)
+        out = torch.empty(nf * self.frame_bytes, dtype=torch.uint8, device=b.device)
+        _lib.check(_lib.lib().bbb_rs_encode(C.c_void_p(b.data_ptr()), nf, C.byref(self._cfg()), C.c_void_p(out.data_ptr()), self.device,
+                                            self._stream_ptr()), "bbb_rs_encode")
+        return out
+
+    def decode(self, coded):
+        """(data, nerr) of whole coded frames in a uint8 or packed int64 CUDA tensor (bbb_rs_decode): the data frames as a uint8
+        CUDA tensor and one uint8 per codeword (frame f, codeword c at f * depth + c): the symbols corrected, 255 where the
+        codeword failed.  Asynchronous on the current torch stream."""
+        b, nf = self._frames("coded", coded, self.frame_bytes)
+        data = torch.empty(nf * self.data_bytes, dtype=torch.uint8, device=b.device)
+        nerr = torch.empty(nf * self.depth, dtype=torch.uint8, device=b.device)
+        if self._stats is None:
+            self._stats = torch.zeros(_lib.RS_NSTATS, dtype=torch.int64, device=b.device)
+        _lib.check(_lib.lib().bbb_rs_decode(C.c_void_p(b.data_ptr()), nf, C.byref(self._cfg()), C.c_void_p(data.data_ptr()),
+                                            C.c_void_p(nerr.data_ptr()), C.c_void_p(self._stats.data_ptr()), self.device, self._stream_ptr()),
+                   "bbb_rs_decode")
+        return data, nerr
+
+    def stream(self):
+        """An RSStream: `push(chunk)` decodes the whole frames that are complete so far, `finish()` says what was left over."""
+        return RSStream(self)
+
+    def stats(self):
+        """What the decoder calls through this object added up (synchronises)."""
+        v = [0] * _lib.RS_NSTATS if self._stats is None else self._stats.cpu().tolist()
+        return dict(zip(("codewords", "clean", "failed", "symbols_corrected", "bits_corrected"), v))
+
+
+class RSStream:
+    """A coded record decoded piece by piece: the bytes of an incomplete frame are held back until the rest arrives, so the
+    pieces give the data and nerr of one call.  Nothing lives on the device between calls but those bytes."""
+
+    def __init__(self, code):
+        self.code, self.held = code, None
+
+    def push(self, chunk):
+        """(data, nerr) of the frames this chunk completes (often none)."""
+        b = _as_bytes("chunk", chunk, self.code.device).reshape(-1)
+        buf = b if self.held is None or not self.held.numel() else torch.cat([self.held, b])
+        whole = buf.numel() // self.code.frame_bytes * self.code.frame_bytes
+        self.held = buf[whole:].clone()
+        return self.code.decode(buf[:whole].contiguous())
+
+    def finish(self):
+        """The record ends here: the number of bytes of a last, incomplete frame, which are dropped."""
+        left = 0 if self.held is None else self.held.numel()
+        self.held = None
+        return left
+
+
+class Concatenated:
+    """The classic concatenation: an outer ReedSolomon around an inner ConvCode.  `decode` has the contract of
+    ConvCode.decode for one final call from step 0, so RX.slice / count_errors / detect take it as `fec=`.  Step 0 of the inner
+    code is bit 0 of frame 0."""
+
+    def __init__(self, outer, inner):
+        if not isinstance(outer, ReedSolomon) or not isinstance(inner, ConvCode):
+            raise ValueError("outer must be a ReedSolomon and inner a ConvCode")
+        if outer.device != inner.device:
+            raise ValueError("outer and inner must live on one device")
+        self.outer, self.inner = outer, inner
+
+    def encode(self, data):
+        """(packed int64 transmitted bits, count) of whole data frames: RS-encoded, then the frames' bits convolutionally encoded
+        from step 0, with K - 1 zero steps appended if the inner code is terminated."""
+        coded = self.outer.encode(data)
+        nbits = 8 * coded.numel() + (self.inner.K - 1 if self.inner.terminated else 0)
+        packed = torch.zeros((nbits + 63) // 64, dtype=torch.int64, device=coded.device)
+        packed.view(torch.uint8)[:coded.numel()] = coded
+        return self.inner.encode(packed, nbits)
+
+    def decode(self, values, hard=False, nbits=None):
+        """(packed int64 data bits, nbits): one final inner decode of the received values (soft int16, or hard packed bits with
+        their count), then the RS decode of the whole frames among the decided steps; a trailing partial frame is dropped."""
+        bits, nd = self.inner.decode(values, hard=hard, nbits=nbits)
+        nf = nd // (8 * self.outer.frame_bytes)
+        data, _ = self.outer.decode(bits.view(torch.uint8)[:nf * self.outer.frame_bytes])
+        out = torch.zeros((data.numel() + 7) // 8, dtype=torch.int64, device=data.device)
+        out.view(torch.uint8)[:data.numel()] = data
+        return out, 8 * data.numel()

@@ -44,7 +44,9 @@ class RX:
         phase itself.  It carries its own filter, threshold and strictness and excludes rx_filter, dfe, mlse and stride.
         fec (a fec.ConvCode): the HARD decisions of whichever path was chosen are received bits of its code, from step 0 on, and
         are decoded in one final call (bbb_conv_decode): the decoded bits and their count come back instead.  Soft decoding
-        goes through ConvCode.decode on the int16 values of FIR.filter, DFE.equalize or TimingRecovery.recover."""
+        goes through ConvCode.decode on the int16 values of FIR.filter, DFE.equalize or TimingRecovery.recover.  fec may also
+        be a fec.Concatenated (a ReedSolomon around a ConvCode): the Viterbi decoder's bytes are RS-decoded as well, and the
+        data bits of the whole frames come back."""
         if fec is not None:
             bits, nbits = self.slice(samples, first_sample, stride, strict, rx_filter, dfe, mlse, timing)
             return fec.decode(bits, hard=True, nbits=nbits)

@@ -42,6 +42,11 @@
 //                       sent as +-64 plus Gaussian noise of sigma 5 nv made on the host, sliced (bbb_rx_slice) and decoded
 //                       from the hard decisions and from the soft values: one JSON line with the channel's errors and both
 //                       decoders' (sigma 40 of the default nv is past what hard decisions survive at rate 3/4; --nv 5 is not)
+//          rs:          --rs I [--eye-samples 1e6] [--prbs 31] [--sigma 42]   the concatenated code (bbb_rs_* around bbb_conv_*): the whole
+//                       CCSDS (255, 223) frames of depth I (1..8) that eye-samples PRBS bits fill, RS-encoded, their bits through
+//                       the K = 7 code (0171, 0133) at rate 1/2, sent as +-64 plus Gaussian noise of sigma made on the host, sliced,
+//                       Viterbi-decoded from the hard decisions and RS-decoded: one JSON line with the bit errors of the channel,
+//                       behind the Viterbi decoder and behind the RS decoder, and the RS decoder's statistics
 //          link:        --link 1 [--eye-samples 1e6] [--prbs 31] [--nv 8] [--shape 16] [--delay 2]   the bathtub of one transmitter
 //                       setting decided on the raw sample (bbb_tx_ber_sweep_*) and behind the moving average of rx.py:24-26
 //                       (bbb_link_sweep_* with the taps of bbb_fir_moving_average, the filtered stream re-timed by `delay`), the
@@ -217,7 +222,7 @@ int main(int argc, char **argv) {
     bool lags_set = false;
     int shape = 16, eye_shift = 4;
     double eye_samples = 1e6;
-    int tx_sweep = 0, nv_lo = 0, nv_hi = 15, fir = 0, dfe = 0, mlse = 0, timing = 0, fec = 0, link = 0, link_delay = 2, errstat = 0, xcorr = 0, ddc = 0, nco_pm = 100;
+    int tx_sweep = 0, nv_lo = 0, nv_hi = 15, fir = 0, dfe = 0, mlse = 0, timing = 0, fec = 0, rs = 0, rs_sigma = 42, link = 0, link_delay = 2, errstat = 0, xcorr = 0, ddc = 0, nco_pm = 100;
     unsigned long errstat_guard = 64;
     unsigned long long init0 = 1;
     double bits = 1e9, from = 0, to = 10, step = 1, loopback = 0, nsamples = 0, grng_eval = 0;
@@ -268,6 +273,8 @@ int main(int argc, char **argv) {
         else if (a == "--mlse") mlse = std::atoi(v);
         else if (a == "--timing") timing = std::atoi(v);
         else if (a == "--fec") fec = std::atoi(v);
+        else if (a == "--rs") rs = std::atoi(v);
+        else if (a == "--sigma") rs_sigma = std::atoi(v);
         else if (a == "--link") link = std::atoi(v);
         else if (a == "--delay") link_delay = std::atoi(v);
         else if (a == "--errstat") errstat = std::atoi(v);
@@ -765,6 +772,62 @@ int main(int argc, char **argv) {
                     "\"seconds\": %.4f}\n", (unsigned long long)nbits, k, fec, cc.keep[0], cc.keep[1], 5 * nv, (unsigned long long)ntx,
                     (unsigned long long)e_channel, (unsigned long long)nd_hard, (unsigned long long)e_hard, (unsigned long long)nd_soft,
                     (unsigned long long)e_soft, secs);
+        return 0;
+    }
+
+    // ---- the concatenated code: Reed-Solomon around the K = 7 code, the closed loop through the C ABI (bbb_rs_*, bbb_conv_*) -----------
+    if (rs) {
+        bbb_rs_cfg rc{};
+        rc.prim_poly = 0x187, rc.fcr = 112, rc.prim = 11, rc.nroots = 32, rc.n = 255, rc.depth = (uint32_t)rs;
+        const uint64_t fdata = 223ull * (uint64_t)(rs > 0 ? rs : 1), fcoded = 255ull * (uint64_t)(rs > 0 ? rs : 1);
+        const uint64_t nframes = eye_samples < 1 ? 0 : (uint64_t)eye_samples / (8 * fdata);
+        if (rs < 1 || rs > 8 || rs_sigma < 0 || rs_sigma > 200 || nframes < 1) {
+            std::fprintf(stderr, "--rs 1..8, --sigma 0..200, --eye-samples at least one frame of 1784 I bits\n");
+            return 2;
+        }
+        bbb_conv_cfg cc{};
+        cc.K = 7, cc.n = 2, cc.gen[0] = 0171, cc.gen[1] = 0133, cc.period = 1, cc.keep[0] = cc.keep[1] = 1;
+        const uint64_t nbits = nframes * fdata * 8, ncoded = nframes * fcoded * 8;
+        uint64_t ntx = 0, nhard = 0, nd = 0, e_viterbi = 0, e_data = 0, e_channel = 0;
+        uint64_t *data = nullptr, *coded = nullptr, *tx = nullptr, *hard = nullptr, *dec = nullptr, *out = nullptr, *stats = nullptr;
+        int16_t *soft = nullptr;
+        if (hipMalloc((void **)&data, (nbits / 64 + 1) * 8) != hipSuccess || hipMalloc((void **)&coded, (ncoded / 64 + 1) * 8) != hipSuccess ||
+            hipMalloc((void **)&tx, (2 * ncoded / 64 + 1) * 8) != hipSuccess || hipMalloc((void **)&hard, (2 * ncoded / 64 + 1) * 8) != hipSuccess ||
+            hipMalloc((void **)&dec, (ncoded / 64 + 1) * 8) != hipSuccess || hipMalloc((void **)&out, (nbits / 64 + 1) * 8) != hipSuccess ||
+            hipMalloc((void **)&stats, BBB_RS_NSTATS * 8) != hipSuccess ||
+            hipMalloc((void **)&soft, 2 * ncoded * sizeof(int16_t)) != hipSuccess || hipMemset(stats, 0, BBB_RS_NSTATS * 8) != hipSuccess ||
+            hipMemset(coded, 0, (ncoded / 64 + 1) * 8) != hipSuccess || hipMemset(out, 0, (nbits / 64 + 1) * 8) != hipSuccess) {
+            std::fprintf(stderr, "hipMalloc failed\n");
+            return 1;
+        }
+        CHECK(bbb_prbs_fill(k, 1, 0, nbits, data, 0, nullptr));
+        const double t0 = now_s();
+        CHECK(bbb_rs_encode((const uint8_t *)data, nframes, &rc, (uint8_t *)coded, 0, nullptr));
+        CHECK(bbb_conv_encode(coded, ncoded, 0, &cc, nullptr, tx, &ntx, 0, nullptr));
+        std::vector<uint64_t> txh((size_t)(ntx + 63) / 64), codedh((size_t)(ncoded + 63) / 64), dech((size_t)(ncoded + 63) / 64);
+        if (hipMemcpy(txh.data(), tx, txh.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) { std::fprintf(stderr, "copy failed\n"); return 1; }
+        std::vector<int16_t> x((size_t)ntx);
+        std::mt19937_64 gen(43);
+        std::normal_distribution<double> noise(0.0, (double)rs_sigma);
+        for (uint64_t i = 0; i < ntx; ++i) x[(size_t)i] = (int16_t)((txh[(size_t)(i >> 6)] >> (i & 63) & 1 ? 64 : -64) + std::lrint(noise(gen)));
+        if (hipMemcpy(soft, x.data(), ntx * sizeof(int16_t), hipMemcpyHostToDevice) != hipSuccess) { std::fprintf(stderr, "copy failed\n"); return 1; }
+        CHECK(bbb_rx_slice(soft, ntx, 1, 0, 0, hard, &nhard, 0, nullptr));
+        CHECK(bbb_conv_decode(hard, 0, nhard, 0, 0, 1, BBB_CONV_HARD, &cc, dec, nullptr, &nd, 0, nullptr));
+        CHECK(bbb_rs_decode((const uint8_t *)dec, nd / (8 * fcoded), &rc, (uint8_t *)out, nullptr, stats, 0, nullptr));
+        CHECK(bbb_prbs_check(k, 1, 0, nd / (8 * fcoded) * fdata * 8, out, &e_data, 0, nullptr));
+        uint64_t st[BBB_RS_NSTATS];
+        if (hipMemcpy(st, stats, sizeof st, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(codedh.data(), coded, codedh.size() * 8, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(dech.data(), dec, dech.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) { std::fprintf(stderr, "copy failed\n"); return 1; }
+        const double secs = now_s() - t0;
+        for (uint64_t i = 0; i < ntx; ++i) e_channel += (uint64_t)((x[(size_t)i] >= 0) != (bool)(txh[(size_t)(i >> 6)] >> (i & 63) & 1));
+        for (uint64_t i = 0; i < nd && i < ncoded; ++i) e_viterbi += (codedh[(size_t)(i >> 6)] ^ dech[(size_t)(i >> 6)]) >> (i & 63) & 1;
+        for (void *p : {(void *)data, (void *)coded, (void *)tx, (void *)hard, (void *)dec, (void *)out, (void *)stats, (void *)soft}) (void)hipFree(p);
+        std::printf("{\"mode\": \"rs\", \"code\": \"ccsds(255,223)\", \"depth\": %d, \"frames\": %llu, \"data_bits\": %llu, \"prbs\": %d, \"sigma\": %d, "
+                    "\"coded_bits\": %llu, \"channel_errors\": %llu, \"viterbi_errors\": %llu, \"data_errors\": %llu, \"codewords\": %llu, \"clean\": %llu, "
+                    "\"failed\": %llu, \"symbols_corrected\": %llu, \"bits_corrected\": %llu, \"seconds\": %.4f}\n", rs, (unsigned long long)nframes,
+                    (unsigned long long)nbits, k, rs_sigma, (unsigned long long)ntx, (unsigned long long)e_channel, (unsigned long long)e_viterbi,
+                    (unsigned long long)e_data, (unsigned long long)st[0], (unsigned long long)st[1], (unsigned long long)st[2], (unsigned long long)st[3],
+                    (unsigned long long)st[4], secs);
         return 0;
     }
 

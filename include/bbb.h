@@ -1094,6 +1094,47 @@ int bbb_errstat_set_stream(bbb_errstat *e, void *hip_stream);
 int bbb_errstat_geometry(uint64_t *tile_bits, uint64_t *wave_bits);
 int bbb_errstat_close(bbb_errstat *e);
 
+/* ---- Reed-Solomon codec over GF(2^8) with symbol interleaving --------------------------------- */
+
+/* The outer code behind the Viterbi decoder (bbb_conv_decode), whose errors come in bursts.
+ * Field: GF(2^8) defined by prim_poly (9 bits, bit 8 set, x of order 255: 0x11D and 0x187 are the usual ones); alpha = x.
+ * Code:  nroots even, 2..32, t = nroots / 2; n = nroots + 1 .. 255 the codeword length (below 255: a shortened code, whose
+ *        missing leading symbols are zero and never stored); k = n - nroots; fcr 0..254; prim 1..254 with gcd(prim, 255) = 1;
+ *        g(x) = prod_{i < nroots} (x - alpha^(prim (fcr + i))).  Systematic: symbol 0 of a codeword is the coefficient of
+ *        x^(n-1), the k data symbols come first, then the nroots parity symbols (the convention of the common software codecs).
+ *        (255, 223) with 0x187, fcr 112, prim 11 is the CCSDS code in the conventional basis.
+ * Interleaving: depth I = 1..8.  A coded frame is I n bytes, byte j is symbol j / I of codeword j % I: the I k data bytes
+ *        unchanged, then I nroots parity bytes.  The encoder's input frame and the decoder's output frame are those I k data
+ *        bytes.  Frame f starts at byte f I n (coded) or f I k (data); no alignment is assumed.
+ * Bytes: byte j of a buffer is bits 8j .. 8j + 7 of the packed bit streams (LSB first in u64 words): the little-endian byte
+ *        view of what bbb_conv_decode writes.
+ * Decoder: bounded distance.  If a codeword of the (shortened) code lies within t symbols of the received word it is unique:
+ *        its data symbols are the output, nerr the number of symbols that differ (0..t), "bits corrected" the popcount of the
+ *        differences.  Otherwise the codeword FAILED: the received data symbols pass through unchanged and nerr = 255 (in
+ *        terms of the error locator: a degree above t, fewer roots than the degree among the n stored positions, or a root
+ *        in a padded position).  Beyond t errors the word found may be another codeword than the one sent.
+ * Out of scope: erasures, soft-decision decoding, the CCSDS dual basis, frame synchronisation, convolutional interleavers.
+ *
+ * nerr (may be NULL): one byte per codeword at index f I + c.  stats (may be NULL, 8-byte aligned) is uint64[BBB_RS_NSTATS],
+ * ADDED TO: codewords, clean codewords, failed codewords, symbols corrected, bits corrected.  nframes = 0 writes nothing.
+ * The device calls are asynchronous on hip_stream and keep no state.  BBB_EINVAL (with a detail, before the device is touched):
+ * anything wrong with cfg (a prim_poly that is not primitive included; reserved must be 0), null pointers, a misaligned
+ * stats_dev, an output that overlaps the input or another output, nframes I n > 2^40. */
+#define BBB_RS_NSTATS 5
+#define BBB_RS_FAILED 255
+typedef struct {
+    uint32_t prim_poly, fcr, prim, nroots, n, depth;
+    uint32_t reserved[2];
+} bbb_rs_cfg;
+int bbb_rs_encode(const uint8_t *data_dev, uint64_t nframes, const bbb_rs_cfg *cfg, uint8_t *out_dev, int device, void *hip_stream);
+/* The same as a serial loop over host memory; works without a GPU. */
+int bbb_rs_encode_host(const uint8_t *data, uint64_t nframes, const bbb_rs_cfg *cfg, uint8_t *out);
+int bbb_rs_decode(const uint8_t *in_dev, uint64_t nframes, const bbb_rs_cfg *cfg, uint8_t *data_dev, uint8_t *nerr_dev /* may be NULL */,
+                  uint64_t *stats_dev /* may be NULL */, int device, void *hip_stream);
+/* The decoder's definition as an independent serial loop over host memory; works without a GPU. */
+int bbb_rs_model_host(const uint8_t *in, uint64_t nframes, const bbb_rs_cfg *cfg, uint8_t *data, uint8_t *nerr /* may be NULL */,
+                      uint64_t *stats /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif
