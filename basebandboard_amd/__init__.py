@@ -21,6 +21,7 @@ from .dfe import DFE, DFEStream                          # noqa: F401
 from .mlse import MLSE, MLSEStream                       # noqa: F401
 from .timing import TimingRecovery, TimingStream         # noqa: F401
 from .fec import ConvCode, ConvStream, ReedSolomon, RSStream, Concatenated  # noqa: F401
+from .framesync import FrameSync, FrameSyncStream        # noqa: F401
 from .link import LinkSweep                              # noqa: F401
 from .errstat import ErrorStats                          # noqa: F401
 from .equalizer import (TxXcorr, capture_xcorr, tx_xcorr, xcorr_counts, pulse_response, mmse_taps,  # noqa: F401

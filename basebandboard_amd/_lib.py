@@ -32,6 +32,8 @@ SYMBOLS = [
     "bbb_timing_plan", "bbb_timing_run", "bbb_timing_model_host",
     "bbb_conv_plan", "bbb_conv_encode", "bbb_conv_encode_host", "bbb_conv_decode", "bbb_conv_model_host",
     "bbb_rs_encode", "bbb_rs_encode_host", "bbb_rs_decode", "bbb_rs_model_host",
+    "bbb_framesync_plan", "bbb_framesync_run", "bbb_frame_extract", "bbb_frame_attach", "bbb_framesync_model_host",
+    "bbb_frame_extract_host", "bbb_frame_attach_host",
 ]
 
 
@@ -137,6 +139,18 @@ class ConvCfg(C.Structure):
 
 
 RS_NSTATS, RS_FAILED = 5, 255
+FRAMESYNC_NSTATE, FRAMESYNC_OVERFLOW, FRAMESYNC_ERROR = 8, 1 << 24, 1 << 25
+
+
+class FrameSyncCfg(C.Structure):
+    """bbb_framesync_cfg"""
+    _fields_ = [("marker", C.c_uint64)] + [(n, C.c_uint32) for n in ("marker_bits", "frame_bits", "tol_search", "tol_lock", "verify", "flywheel",
+                                                                    "both_polarities", "rand_poly", "rand_seed")] + [("reserved", C.c_uint32 * 3)]
+
+
+class FrameSyncPlan(C.Structure):
+    """bbb_framesync_plan_out"""
+    _fields_ = [(n, C.c_uint64) for n in ("scratch_bytes", "holdback_bits", "tile_bits")]
 
 
 class RSCfg(C.Structure):
@@ -323,6 +337,14 @@ def lib():
     l.bbb_rs_encode_host.argtypes = [vp, u64, C.POINTER(RSCfg), vp]
     l.bbb_rs_decode.argtypes = [vp, u64, C.POINTER(RSCfg), vp, vp, vp, i32, vp]
     l.bbb_rs_model_host.argtypes = [vp, u64, C.POINTER(RSCfg), vp, vp, vp]
+    fsc = C.POINTER(FrameSyncCfg)
+    l.bbb_framesync_plan.argtypes = [u64, fsc, C.POINTER(FrameSyncPlan)]
+    l.bbb_framesync_run.argtypes = [vp, u64, u64, i32, fsc, vp, vp, vp, u64, vp, i32, vp]
+    l.bbb_frame_extract.argtypes = [vp, u64, u64, vp, vp, vp, u64, fsc, vp, i32, vp]
+    l.bbb_frame_attach.argtypes = [vp, u64, fsc, vp, i32, vp]
+    l.bbb_framesync_model_host.argtypes = [vp, u64, u64, i32, fsc, vp, vp, vp, u64]
+    l.bbb_frame_extract_host.argtypes = [vp, u64, u64, vp, vp, vp, u64, fsc, vp]
+    l.bbb_frame_attach_host.argtypes = [vp, u64, fsc, vp]
     u8p = C.POINTER(C.c_uint8)
     l.bbb_gf2_berlekamp_massey.argtypes = [u8p, u64, u8p, C.POINTER(C.c_int64)]
     l.bbb_gf2_recur.argtypes = [i32, i32, u64p, u8p, i32, u8p]

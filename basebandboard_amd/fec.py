@@ -17,7 +17,7 @@ threshold, so the caller SUBTRACTS THE THRESHOLD FIRST where it is not 0 (and ke
 
 A Viterbi decoder leaves its errors in bursts.  `ReedSolomon` (include/bbb.h, bbb_rs_*) is the outer code that removes them: an
 exact Reed-Solomon codec over GF(2^8) whose codewords are interleaved symbol by symbol to depth 1..8, and `Concatenated(outer,
-inner)` is the pair as one `fec=`.
+inner)` is the pair as one `fec=`; with `sync=` (a framesync.FrameSync) it marks its frames and finds them again.
 """
 import ctypes as C
 from fractions import Fraction
@@ -26,6 +26,7 @@ import torch
 
 from . import _lib
 from .fir import Carry
+from .framesync import FrameSync
 
 PRESETS = {"2/3": (2, (0b01, 0b11)), "3/4": (3, (0b101, 0b011)), "5/6": (5, (0b10101, 0b01011)), "7/8": (7, (0b1010001, 0b0101111))}
 DEFAULTS = (192, 64, 64)
@@ -198,7 +199,8 @@ class ReedSolomon:
     codeword; the field is `prim_poly`'s, the generator's roots alpha^(prim (fcr + i)); `depth` codewords are interleaved symbol
     by symbol into a frame of depth * n bytes whose first depth * k bytes are the data unchanged.  The decoder is a
     bounded-distance decoder: a codeword with more than t wrong symbols FAILS (its data pass through, nerr 255) or, rarely,
-    decodes to another codeword.  No erasures, no soft decisions, no dual basis, no frame synchronisation."""
+    decodes to another codeword.  No erasures, no soft decisions, no dual basis.  The frames must start at byte 0:
+    framesync.FrameSync finds them in a stream that does not."""
 
     def __init__(self, n=255, k=223, prim_poly=0x11D, fcr=0, prim=1, depth=1, device=0):
         self.n, self.k, self.prim_poly, self.fcr, self.prim, self.depth, self.device = (int(v) for v in (n, k, prim_poly, fcr, prim, depth, device))
@@ -307,29 +309,51 @@ class RSStream:
 
 class Concatenated:
     """The classic concatenation: an outer ReedSolomon around an inner ConvCode.  `decode` has the contract of
-    ConvCode.decode for one final call from step 0, so RX.slice / count_errors / detect take it as `fec=`.  Step 0 of the inner
-    code is bit 0 of frame 0."""
+    ConvCode.decode for one final call from step 0, so RX.slice / count_errors / detect take it as `fec=`.  Without `sync`,
+    step 0 of the inner code is bit 0 of frame 0.  With sync (a framesync.FrameSync whose payload is one coded frame), `encode`
+    attaches a marker to every coded frame (and randomises it, if the FrameSync does) and `decode` finds the frames among the
+    Viterbi decoder's bits wherever they start and whichever polarity they have, and hands those to the Reed-Solomon decoder."""
 
-    def __init__(self, outer, inner):
+    def __init__(self, outer, inner, sync=None):
         if not isinstance(outer, ReedSolomon) or not isinstance(inner, ConvCode):
             raise ValueError("outer must be a ReedSolomon and inner a ConvCode")
         if outer.device != inner.device:
             raise ValueError("outer and inner must live on one device")
-        self.outer, self.inner = outer, inner
+        if sync is not None:
+            if not isinstance(sync, FrameSync):
+                raise ValueError("sync must be a FrameSync")
+            if sync.device != outer.device:
+                raise ValueError("sync must live on the codes' device")
+            if sync.payload_bytes != outer.frame_bytes:
+                raise ValueError(f"sync's payload must be one coded frame of {outer.frame_bytes} bytes")
+        self.outer, self.inner, self.sync = outer, inner, sync
 
     def encode(self, data):
-        """(packed int64 transmitted bits, count) of whole data frames: RS-encoded, then the frames' bits convolutionally encoded
-        from step 0, with K - 1 zero steps appended if the inner code is terminated."""
+        """(packed int64 transmitted bits, count) of whole data frames: RS-encoded, markers attached if there is a `sync`, then
+        the frames' bits convolutionally encoded from step 0, with K - 1 zero steps appended if the inner code is terminated."""
         coded = self.outer.encode(data)
-        nbits = 8 * coded.numel() + (self.inner.K - 1 if self.inner.terminated else 0)
+        tail = self.inner.K - 1 if self.inner.terminated else 0
+        if self.sync is not None:
+            framed, nframed = self.sync.attach(coded)
+            packed = torch.zeros((nframed + tail + 63) // 64, dtype=torch.int64, device=coded.device)
+            packed[:framed.numel()] = framed
+            return self.inner.encode(packed, nframed + tail)
+        nbits = 8 * coded.numel() + tail
         packed = torch.zeros((nbits + 63) // 64, dtype=torch.int64, device=coded.device)
         packed.view(torch.uint8)[:coded.numel()] = coded
         return self.inner.encode(packed, nbits)
 
     def decode(self, values, hard=False, nbits=None):
         """(packed int64 data bits, nbits): one final inner decode of the received values (soft int16, or hard packed bits with
-        their count), then the RS decode of the whole frames among the decided steps; a trailing partial frame is dropped."""
+        their count), then the RS decode of the whole frames among the decided steps; a trailing partial frame is dropped.
+        With a `sync` the frames are those it finds (this reads their number back: it synchronises)."""
         bits, nd = self.inner.decode(values, hard=hard, nbits=nbits)
+        if self.sync is not None:
+            frames, _ = self.sync.sync(bits, nd)
+            data, _ = self.outer.decode(frames.contiguous())
+            out = torch.zeros((data.numel() + 7) // 8, dtype=torch.int64, device=data.device)
+            out.view(torch.uint8)[:data.numel()] = data
+            return out, 8 * data.numel()
         nf = nd // (8 * self.outer.frame_bytes)
         data, _ = self.outer.decode(bits.view(torch.uint8)[:nf * self.outer.frame_bytes])
         out = torch.zeros((data.numel() + 7) // 8, dtype=torch.int64, device=data.device)

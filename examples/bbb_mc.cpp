@@ -47,6 +47,10 @@
 //                       the K = 7 code (0171, 0133) at rate 1/2, sent as +-64 plus Gaussian noise of sigma made on the host, sliced,
 //                       Viterbi-decoded from the hard decisions and RS-decoded: one JSON line with the bit errors of the channel,
 //                       behind the Viterbi decoder and behind the RS decoder, and the RS decoder's statistics
+//                       --sync J with --rs: a CCSDS marker attached to every coded frame and the payload randomised
+//                       (bbb_frame_attach), J >= 0 random bits put in front, the whole channel inverted; behind the Viterbi decoder
+//                       the frames are found and cut out (bbb_framesync_run, bbb_frame_extract; tol_search 2, tol_lock 6, verify 1,
+//                       flywheel 2) and handed to the RS decoder; the line gains the synchroniser's counters
 //          link:        --link 1 [--eye-samples 1e6] [--prbs 31] [--nv 8] [--shape 16] [--delay 2]   the bathtub of one transmitter
 //                       setting decided on the raw sample (bbb_tx_ber_sweep_*) and behind the moving average of rx.py:24-26
 //                       (bbb_link_sweep_* with the taps of bbb_fir_moving_average, the filtered stream re-timed by `delay`), the
@@ -222,7 +226,7 @@ int main(int argc, char **argv) {
     bool lags_set = false;
     int shape = 16, eye_shift = 4;
     double eye_samples = 1e6;
-    int tx_sweep = 0, nv_lo = 0, nv_hi = 15, fir = 0, dfe = 0, mlse = 0, timing = 0, fec = 0, rs = 0, rs_sigma = 42, link = 0, link_delay = 2, errstat = 0, xcorr = 0, ddc = 0, nco_pm = 100;
+    int tx_sweep = 0, nv_lo = 0, nv_hi = 15, fir = 0, dfe = 0, mlse = 0, timing = 0, fec = 0, rs = 0, rs_sigma = 42, sync_junk = -1, link = 0, link_delay = 2, errstat = 0, xcorr = 0, ddc = 0, nco_pm = 100;
     unsigned long errstat_guard = 64;
     unsigned long long init0 = 1;
     double bits = 1e9, from = 0, to = 10, step = 1, loopback = 0, nsamples = 0, grng_eval = 0;
@@ -275,6 +279,7 @@ int main(int argc, char **argv) {
         else if (a == "--fec") fec = std::atoi(v);
         else if (a == "--rs") rs = std::atoi(v);
         else if (a == "--sigma") rs_sigma = std::atoi(v);
+        else if (a == "--sync") sync_junk = std::atoi(v);
         else if (a == "--link") link = std::atoi(v);
         else if (a == "--delay") link_delay = std::atoi(v);
         else if (a == "--errstat") errstat = std::atoi(v);
@@ -781,13 +786,18 @@ int main(int argc, char **argv) {
         rc.prim_poly = 0x187, rc.fcr = 112, rc.prim = 11, rc.nroots = 32, rc.n = 255, rc.depth = (uint32_t)rs;
         const uint64_t fdata = 223ull * (uint64_t)(rs > 0 ? rs : 1), fcoded = 255ull * (uint64_t)(rs > 0 ? rs : 1);
         const uint64_t nframes = eye_samples < 1 ? 0 : (uint64_t)eye_samples / (8 * fdata);
-        if (rs < 1 || rs > 8 || rs_sigma < 0 || rs_sigma > 200 || nframes < 1) {
-            std::fprintf(stderr, "--rs 1..8, --sigma 0..200, --eye-samples at least one frame of 1784 I bits\n");
+        if (rs < 1 || rs > 8 || rs_sigma < 0 || rs_sigma > 200 || nframes < 1 || sync_junk < -1 || sync_junk > (1 << 20)) {
+            std::fprintf(stderr, "--rs 1..8, --sigma 0..200, --eye-samples at least one frame of 1784 I bits, --sync 0..2^20\n");
             return 2;
         }
         bbb_conv_cfg cc{};
         cc.K = 7, cc.n = 2, cc.gen[0] = 0171, cc.gen[1] = 0133, cc.period = 1, cc.keep[0] = cc.keep[1] = 1;
-        const uint64_t nbits = nframes * fdata * 8, ncoded = nframes * fcoded * 8;
+        const bool sync = sync_junk >= 0;
+        bbb_framesync_cfg fc{};
+        fc.marker = 0x1DFCCF1A, fc.marker_bits = 32, fc.frame_bits = 32 + 8 * (uint32_t)fcoded, fc.tol_search = 2, fc.tol_lock = 6, fc.verify = 1;
+        fc.flywheel = 2, fc.both_polarities = 1, fc.rand_poly = 0x1A9, fc.rand_seed = 0xFF;
+        // ncoded: the bits that go into the convolutional encoder: the coded frames, or the junk and the marked frames
+        const uint64_t nbits = nframes * fdata * 8, nplain = nframes * fcoded * 8, ncoded = sync ? (uint64_t)sync_junk + nframes * fc.frame_bits : nplain;
         uint64_t ntx = 0, nhard = 0, nd = 0, e_viterbi = 0, e_data = 0, e_channel = 0;
         uint64_t *data = nullptr, *coded = nullptr, *tx = nullptr, *hard = nullptr, *dec = nullptr, *out = nullptr, *stats = nullptr;
         int16_t *soft = nullptr;
@@ -802,26 +812,66 @@ int main(int argc, char **argv) {
         }
         CHECK(bbb_prbs_fill(k, 1, 0, nbits, data, 0, nullptr));
         const double t0 = now_s();
-        CHECK(bbb_rs_encode((const uint8_t *)data, nframes, &rc, (uint8_t *)coded, 0, nullptr));
+        std::mt19937_64 gen(43);
+        uint64_t *frames = nullptr, *fstate = nullptr, *fpos = nullptr, *fscratch = nullptr;
+        uint16_t *fmeta = nullptr;
+        bbb_framesync_plan_out plan{};
+        if (!sync) {
+            CHECK(bbb_rs_encode((const uint8_t *)data, nframes, &rc, (uint8_t *)coded, 0, nullptr));
+        } else {
+            CHECK(bbb_framesync_plan(ncoded, &fc, &plan));
+            if (hipMalloc((void **)&frames, (nplain / 64 + 1) * 8) != hipSuccess || hipMalloc((void **)&fstate, BBB_FRAMESYNC_NSTATE * 8) != hipSuccess ||
+                hipMalloc((void **)&fpos, (nframes + 1) * 8) != hipSuccess || hipMalloc((void **)&fmeta, (nframes + 1) * 2) != hipSuccess ||
+                hipMalloc((void **)&fscratch, plan.scratch_bytes) != hipSuccess || hipMemset(fstate, 0, BBB_FRAMESYNC_NSTATE * 8) != hipSuccess) {
+                std::fprintf(stderr, "hipMalloc failed\n");
+                return 1;
+            }
+            // RS-encode into `frames`, attach into `dec` (free until the decoder runs), then junk in front on the host
+            CHECK(bbb_rs_encode((const uint8_t *)data, nframes, &rc, (uint8_t *)frames, 0, nullptr));
+            CHECK(bbb_frame_attach((const uint8_t *)frames, nframes, &fc, dec, 0, nullptr));
+            const uint64_t nmarked = nframes * fc.frame_bits;
+            std::vector<uint64_t> marked((size_t)(nmarked + 63) / 64), line((size_t)(ncoded / 64 + 1), 0);
+            if (hipMemcpy(marked.data(), dec, marked.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) { std::fprintf(stderr, "copy failed\n"); return 1; }
+            for (uint64_t i = 0; i < ncoded; ++i) {
+                const uint64_t b = i < (uint64_t)sync_junk ? gen() & 1 : marked[(size_t)((i - sync_junk) >> 6)] >> ((i - sync_junk) & 63) & 1;
+                line[(size_t)(i >> 6)] |= b << (i & 63);
+            }
+            if (hipMemcpy(coded, line.data(), line.size() * 8, hipMemcpyHostToDevice) != hipSuccess) { std::fprintf(stderr, "copy failed\n"); return 1; }
+        }
         CHECK(bbb_conv_encode(coded, ncoded, 0, &cc, nullptr, tx, &ntx, 0, nullptr));
         std::vector<uint64_t> txh((size_t)(ntx + 63) / 64), codedh((size_t)(ncoded + 63) / 64), dech((size_t)(ncoded + 63) / 64);
         if (hipMemcpy(txh.data(), tx, txh.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) { std::fprintf(stderr, "copy failed\n"); return 1; }
         std::vector<int16_t> x((size_t)ntx);
-        std::mt19937_64 gen(43);
         std::normal_distribution<double> noise(0.0, (double)rs_sigma);
-        for (uint64_t i = 0; i < ntx; ++i) x[(size_t)i] = (int16_t)((txh[(size_t)(i >> 6)] >> (i & 63) & 1 ? 64 : -64) + std::lrint(noise(gen)));
+        const int one = sync ? -64 : 64;              // with --sync the whole channel is inverted
+        for (uint64_t i = 0; i < ntx; ++i) x[(size_t)i] = (int16_t)((txh[(size_t)(i >> 6)] >> (i & 63) & 1 ? one : -one) + std::lrint(noise(gen)));
         if (hipMemcpy(soft, x.data(), ntx * sizeof(int16_t), hipMemcpyHostToDevice) != hipSuccess) { std::fprintf(stderr, "copy failed\n"); return 1; }
         CHECK(bbb_rx_slice(soft, ntx, 1, 0, 0, hard, &nhard, 0, nullptr));
         CHECK(bbb_conv_decode(hard, 0, nhard, 0, 0, 1, BBB_CONV_HARD, &cc, dec, nullptr, &nd, 0, nullptr));
-        CHECK(bbb_rs_decode((const uint8_t *)dec, nd / (8 * fcoded), &rc, (uint8_t *)out, nullptr, stats, 0, nullptr));
-        CHECK(bbb_prbs_check(k, 1, 0, nd / (8 * fcoded) * fdata * 8, out, &e_data, 0, nullptr));
+        uint64_t nfound = nd / (8 * fcoded), fs[BBB_FRAMESYNC_NSTATE] = {0};
+        if (sync) {
+            CHECK(bbb_framesync_run(dec, nd, 0, 1, &fc, fstate, fpos, fmeta, nframes, fscratch, 0, nullptr));
+            CHECK(bbb_frame_extract(dec, nd, 0, fpos, fmeta, fstate, nframes, &fc, (uint8_t *)frames, 0, nullptr));
+            if (hipMemcpy(fs, fstate, sizeof fs, hipMemcpyDeviceToHost) != hipSuccess) { std::fprintf(stderr, "copy failed\n"); return 1; }
+            nfound = std::min<uint64_t>(fs[0] >> 32, nframes);
+        }
+        CHECK(bbb_rs_decode(sync ? (const uint8_t *)frames : (const uint8_t *)dec, nfound, &rc, (uint8_t *)out, nullptr, stats, 0, nullptr));
+        CHECK(bbb_prbs_check(k, 1, 0, nfound * fdata * 8, out, &e_data, 0, nullptr));
+        e_data += (nframes - nfound) * fdata * 8;     // a frame that was not found is all wrong
         uint64_t st[BBB_RS_NSTATS];
         if (hipMemcpy(st, stats, sizeof st, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(codedh.data(), coded, codedh.size() * 8, hipMemcpyDeviceToHost) != hipSuccess ||
             hipMemcpy(dech.data(), dec, dech.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) { std::fprintf(stderr, "copy failed\n"); return 1; }
         const double secs = now_s() - t0;
-        for (uint64_t i = 0; i < ntx; ++i) e_channel += (uint64_t)((x[(size_t)i] >= 0) != (bool)(txh[(size_t)(i >> 6)] >> (i & 63) & 1));
-        for (uint64_t i = 0; i < nd && i < ncoded; ++i) e_viterbi += (codedh[(size_t)(i >> 6)] ^ dech[(size_t)(i >> 6)]) >> (i & 63) & 1;
-        for (void *p : {(void *)data, (void *)coded, (void *)tx, (void *)hard, (void *)dec, (void *)out, (void *)stats, (void *)soft}) (void)hipFree(p);
+        for (uint64_t i = 0; i < ntx; ++i) e_channel += (uint64_t)((x[(size_t)i] >= 0) != ((bool)(txh[(size_t)(i >> 6)] >> (i & 63) & 1) != sync));
+        for (uint64_t i = 0; i < nd && i < ncoded; ++i) e_viterbi += ((codedh[(size_t)(i >> 6)] ^ dech[(size_t)(i >> 6)]) >> (i & 63) & 1) ^ (uint64_t)sync;
+        for (void *p : {(void *)data, (void *)coded, (void *)tx, (void *)hard, (void *)dec, (void *)out, (void *)stats, (void *)soft, (void *)frames,
+                        (void *)fstate, (void *)fpos, (void *)fmeta, (void *)fscratch})
+            if (p) (void)hipFree(p);
+        if (sync)
+            std::printf("{\"mode\": \"sync\", \"junk_bits\": %d, \"inverted\": %llu, \"frames_found\": %llu, \"flywheeled\": %llu, \"acquisitions\": %llu, "
+                        "\"losses\": %llu, \"rejected\": %llu, \"marker_bit_errors\": %llu}\n", sync_junk, (unsigned long long)(fs[0] >> 8 & 1),
+                        (unsigned long long)fs[2], (unsigned long long)fs[3], (unsigned long long)fs[4], (unsigned long long)fs[5], (unsigned long long)fs[6],
+                        (unsigned long long)fs[7]);
         std::printf("{\"mode\": \"rs\", \"code\": \"ccsds(255,223)\", \"depth\": %d, \"frames\": %llu, \"data_bits\": %llu, \"prbs\": %d, \"sigma\": %d, "
                     "\"coded_bits\": %llu, \"channel_errors\": %llu, \"viterbi_errors\": %llu, \"data_errors\": %llu, \"codewords\": %llu, \"clean\": %llu, "
                     "\"failed\": %llu, \"symbols_corrected\": %llu, \"bits_corrected\": %llu, \"seconds\": %.4f}\n", rs, (unsigned long long)nframes,

@@ -1113,7 +1113,8 @@ int bbb_errstat_close(bbb_errstat *e);
  *        differences.  Otherwise the codeword FAILED: the received data symbols pass through unchanged and nerr = 255 (in
  *        terms of the error locator: a degree above t, fewer roots than the degree among the n stored positions, or a root
  *        in a padded position).  Beyond t errors the word found may be another codeword than the one sent.
- * Out of scope: erasures, soft-decision decoding, the CCSDS dual basis, frame synchronisation, convolutional interleavers.
+ * Out of scope: erasures, soft-decision decoding, the CCSDS dual basis, convolutional interleavers.  (Frames that do not start
+ *        at byte 0: bbb_framesync_run and bbb_frame_extract below.)
  *
  * nerr (may be NULL): one byte per codeword at index f I + c.  stats (may be NULL, 8-byte aligned) is uint64[BBB_RS_NSTATS],
  * ADDED TO: codewords, clean codewords, failed codewords, symbols corrected, bits corrected.  nframes = 0 writes nothing.
@@ -1134,6 +1135,92 @@ int bbb_rs_decode(const uint8_t *in_dev, uint64_t nframes, const bbb_rs_cfg *cfg
 /* The decoder's definition as an independent serial loop over host memory; works without a GPU. */
 int bbb_rs_model_host(const uint8_t *in, uint64_t nframes, const bbb_rs_cfg *cfg, uint8_t *data, uint8_t *nerr /* may be NULL */,
                       uint64_t *stats /* may be NULL */);
+
+/* ---- Frame synchroniser: marker search, lock, derandomiser ------------------------------------ */
+
+/* Finds the frames of a packed bit stream that starts anywhere: in front of bbb_rs_decode, behind bbb_conv_decode.
+ * Bit order: stream bit j is bit j % 64 of word j / 64; byte j of a buffer is stream bits 8j .. 8j + 7, bit 8j the least
+ *        significant.  Positions are ABSOLUTE: bit 0 of a call's data is position first_bit, N = first_bit + nbits its end.
+ * Config: marker: bit i is compared with stream bit p + i; marker_bits M 8..64 (bits of marker above M must be 0); frame_bits F,
+ *        marker included, M + 8 <= F <= 2^20; tol_search <= tol_lock <= M / 4; verify v 0..7; flywheel w 0..7; both_polarities
+ *        0 or 1; rand_poly 0 (no randomiser) or 9 bits with the x^8 and x^0 terms set; rand_seed 1..255 (looked at only with a
+ *        rand_poly); reserved 0.
+ * Distance: dist(p, pol) = the number of i < M with bit[p + i] != marker_i ^ pol; a position whose marker does not lie wholly
+ *        inside the data (p + M > N) has distance M + 1.  pol is 0, or also 1 with both_polarities.  As tol_lock <= M / 4 a
+ *        position is within tolerance in one polarity at most.
+ * The machine is serial and causal; this is the definition.
+ *   SEARCH at s: the smallest p >= s and a pol with dist(p, pol) <= tol_search (a CANDIDATE) and dist(p + j F, pol) <=
+ *        tol_lock for j = 1..v: acquisitions += 1, go to LOCK at e = p with that polarity and 0 misses.  Every candidate
+ *        passed over because a confirmation failed: rejected += 1.
+ *   LOCK at e: a step is taken when e + F <= N.  dist(e, pol) <= tol_lock: misses = 0, the frame at e is emitted.  Otherwise
+ *        misses += 1; if misses > w the lock is lost: nothing is emitted, losses += 1, misses = 0, SEARCH at s = e; else the
+ *        frame is emitted as flywheeled.  After an emitted frame e += F.
+ *   A call that is not final stops at the first point it cannot decide yet and leaves its state there: a position p in SEARCH
+ *        needs p + M <= N, a candidate p + v F + M <= N, a LOCK step e + F <= N.  So it never needs bits older than
+ *        N - (max(v, 1) F + M): a stream can hold back that many bits, rounded up to words (bbb_framesync_plan).
+ *   A final call: what lies beyond N is no hit (a candidate whose confirmation does not lie inside the data is rejected), a
+ *        frame that does not end inside the data is not emitted; SEARCH ends at the first p >= s with p + M > N.
+ *   Cutting invariance: any cutting of a record into non-final calls plus one final call gives the frames, counters and state
+ *        of one final call.  Each call's data must begin at or before the state's position.
+ * State: uint64[BBB_FRAMESYNC_NSTATE] on the device, all zero = SEARCH at 0.  Word 0 packs: bits 0..7 mode (0 SEARCH, 1 LOCK; a
+ *        state with another mode, or with bits set that are not named here, was not written by these calls: undefined),
+ *        bit 8 polarity, bit 9 "the next frame emitted is the first of its acquisition", bits 16..23 misses, bit 24 overflow
+ *        (more frames than max_frames in some call), bit 25 ERROR (the data began behind the state's position: the call set
+ *        this bit and wrote nothing else; sticky), bits 32..63 the frames the LAST call emitted (written or not).  Word 1: the
+ *        position (s or e).  Words 2..7, added to: frames, flywheeled, acquisitions, losses, rejected, marker_bit_errors (the
+ *        sum of the distances of the emitted frames that were hits).
+ * Records: a call writes its frames from index 0, in order: pos[i] the absolute position of the marker's first bit; meta[i]
+ *        bits 0..6 the distance in the episode's polarity, bit 8 the polarity, bit 9 flywheeled, bit 10 first frame of an
+ *        acquisition.  Beyond max_frames frames are counted but not written and the overflow bit is set.
+ * Randomiser: the register s starts at rand_seed at every frame; a step gives the bit s & 1 and then s = s >> 1 | parity(s &
+ *        rand_poly & 0xFF) << 7.  The bits are packed into table bytes most significant first, so the table equals the
+ *        standards' byte tables: x^8 + x^7 + x^5 + x^3 + 1 (0x1A9) from 0xFF gives FF 48 0E C0 9A 0D 70 BC ..., period 255.
+ *        Table byte j % period is XORed onto payload byte j (payload byte j = frame bits M + 8j .. M + 8j + 7).
+ * CCSDS preset: the buffer bytes 1A CF FC 1D, that is marker = 0x1DFCCF1A, M = 32, the randomiser above, F = 32 + 8 depth 255.
+ *        This is CCSDS at the BYTE level: the order of the bits within a byte on the channel is this project's (least
+ *        significant first), not the standard's.
+ * Out of scope: bit-slip windows in lock, node synchronisation of the inner code (which received bit is the first of a step),
+ *        soft-decision correlation, convolutional interleavers, markers longer than 64 bits.
+ *
+ * bbb_framesync_plan (host only): the scratch of a run over nbits, the hold-back in bits (a multiple of 64) and the bits one
+ * workgroup of the search pass covers (a multiple of 64), so that tests can aim at its boundaries.
+ * bbb_framesync_run: asynchronous on hip_stream, no host round trip.  in_packed_dev: ceil(nbits / 64) words, 8-byte aligned;
+ * state_dev 8-byte, pos_dev 8-byte, meta_dev 2-byte, scratch_dev 8-byte aligned, scratch of plan's size.
+ * bbb_frame_extract: the payloads of the first min(frames of the last call, max_frames) records, frame i at out[i (F - M) / 8 ...]:
+ * complemented where the record's polarity bit is set, then derandomised.  The count is read from state_dev on the device.
+ * Needs (F - M) % 8 == 0 and out_dev 8-byte aligned with room for max_frames payloads; a record that does not lie inside the
+ * data gives a payload of zeros.
+ * bbb_frame_attach: frame i (marker, then the randomised payload i) at bit i F of out_packed_dev, ceil(nframes F / 64) words
+ * (the bits behind the last frame are 0); payload i is the (F - M) / 8 bytes at payload_dev + i (F - M) / 8.
+ * The *_host forms are the same as plain serial loops over host memory (state, records and all); they share no code with the
+ * kernels and work without a GPU.
+ * BBB_EINVAL (with a detail, before the device is touched): everything wrong with cfg, null or misaligned pointers, any two
+ * buffers of a call that overlap (outputs with inputs and with each other, and, stricter than needed, two inputs), nbits > 2^35, first_bit + nbits > 2^48, nframes F > 2^40. */
+#define BBB_FRAMESYNC_NSTATE 8
+#define BBB_FRAMESYNC_ERROR (1ull << 25)
+#define BBB_FRAMESYNC_OVERFLOW (1ull << 24)
+typedef struct {
+    uint64_t marker;
+    uint32_t marker_bits, frame_bits, tol_search, tol_lock, verify, flywheel, both_polarities, rand_poly, rand_seed;
+    uint32_t reserved[3];
+} bbb_framesync_cfg;
+typedef struct {
+    uint64_t scratch_bytes, holdback_bits, tile_bits;
+} bbb_framesync_plan_out;
+int bbb_framesync_plan(uint64_t nbits, const bbb_framesync_cfg *cfg, bbb_framesync_plan_out *out);
+int bbb_framesync_run(const uint64_t *in_packed_dev, uint64_t nbits, uint64_t first_bit, int final, const bbb_framesync_cfg *cfg,
+                      uint64_t *state_dev, uint64_t *pos_dev, uint16_t *meta_dev, uint64_t max_frames, void *scratch_dev, int device,
+                      void *hip_stream);
+int bbb_frame_extract(const uint64_t *in_packed_dev, uint64_t nbits, uint64_t first_bit, const uint64_t *pos_dev, const uint16_t *meta_dev,
+                      const uint64_t *state_dev, uint64_t max_frames, const bbb_framesync_cfg *cfg, uint8_t *out_dev, int device,
+                      void *hip_stream);
+int bbb_frame_attach(const uint8_t *payload_dev, uint64_t nframes, const bbb_framesync_cfg *cfg, uint64_t *out_packed_dev, int device,
+                     void *hip_stream);
+int bbb_framesync_model_host(const uint64_t *in_packed, uint64_t nbits, uint64_t first_bit, int final, const bbb_framesync_cfg *cfg,
+                             uint64_t *state, uint64_t *pos, uint16_t *meta, uint64_t max_frames);
+int bbb_frame_extract_host(const uint64_t *in_packed, uint64_t nbits, uint64_t first_bit, const uint64_t *pos, const uint16_t *meta,
+                           const uint64_t *state, uint64_t max_frames, const bbb_framesync_cfg *cfg, uint8_t *out);
+int bbb_frame_attach_host(const uint8_t *payload, uint64_t nframes, const bbb_framesync_cfg *cfg, uint64_t *out_packed);
 
 #ifdef __cplusplus
 }
