@@ -3,6 +3,8 @@ import numpy as np
 import pytest
 import torch
 
+import far
+
 pytestmark = pytest.mark.gpu
 
 
@@ -40,16 +42,17 @@ def test_n256_matches_oracle(gpu, oracle, nsamples, first):
 
 
 def test_n256_far_offset(gpu, oracle):
-    """first_step far beyond what the sequential oracle can reach: jump-ahead composes
-    (state_at(a + b) from a handle seeded with state_at(a)), and the stream from there matches
-    the oracle started at that state."""
+    """first_step far beyond what the sequential oracle can reach: the state there comes from the oracle's own jump
+    (oracle/jump.py: x^N mod p by single oracle steps), the product's jump-ahead equals it and composes
+    (state_at(a + b) from a handle seeded with state_at(a)), and the stream from there matches the oracle started
+    at that state."""
     u = gpu.LUTOPT.shipped(256)
-    far = 10**15 + 12345
-    s_far = u.state_at(far)
-    assert gpu.LUTOPT.shipped(256, init=u.state_at(10**15)).state_at(12345) == s_far
     m = oracle.Lutopt(path=oracle.data_path(256))
-    assert m.run_int(u.state_at(10**15 + 12000), 345) == s_far
-    got = gpu.CLTGRNG(u).generate(500_000, first_step=far).cpu().numpy()
+    far_step = 10**15 + 12345
+    s_far = far.lutopt_state(u, m, far_step)
+    assert gpu.LUTOPT.shipped(256, init=far.lutopt_state(u, m, 10**15)).state_at(12345) == s_far
+    assert m.run_int(far.lutopt_state(u, m, 10**15 + 12000), 345) == s_far
+    got = gpu.CLTGRNG(u).generate(500_000, first_step=far_step).cpu().numpy()
     assert np.array_equal(got, m.awgn(s_far, 0, 500_000, fast=True))
 
 
@@ -68,7 +71,7 @@ def test_n256_large_seams_and_checksum(gpu, oracle):
     assert np.array_equal(a_np[:200_000], head)
     rng = np.random.default_rng(0)
     for off in list(rng.integers(0, n - 5000, size=40)) + [n - 5000]:
-        exp = m.awgn(u.state_at(16 + int(off)), 0, 5000, fast=True)
+        exp = m.awgn(far.lutopt_state(u, m, 16 + int(off)), 0, 5000, fast=True)
         assert np.array_equal(a_np[off: off + 5000], exp), off
     # moments of the CLT output (rng.py:63-65 / clt-grng-evaluate.py:18-31): mean 0, variance 64
     x = a_np[: 1 << 24].astype(np.float64)
@@ -98,7 +101,7 @@ def test_small_generated_kernels_ragged(gpu, oracle, n, nsamples, first, init):
     u = gpu.LUTOPT.shipped(n, init=init)
     got = gpu.CLTGRNG(u).generate(nsamples, first_step=first).cpu().numpy()
     m = oracle.Lutopt(path=oracle.data_path(n))
-    exp = m.awgn(u.state_at(first), 0, nsamples)
+    exp = m.awgn(far.lutopt_state(u, m, first), 0, nsamples)
     assert np.array_equal(got, exp)
     assert got.min() >= -(n // 2) and got.max() < n // 2            # a log2(n)-bit signed value (rng.py:78)
 
@@ -121,7 +124,7 @@ def test_n512_int16(gpu, oracle):
     assert g.dtype == torch.int16
     got = g.generate(20_000, first_step=18).cpu().numpy()
     m = oracle.Lutopt(path=oracle.data_path(512))
-    x = u.state_at(18)
+    x = far.lutopt_state(u, m, 18)
     exp = []
     for _ in range(300):
         x = m.step_int(x)
@@ -189,7 +192,7 @@ def test_n256_beyond_4g_samples(gpu, oracle):
     offs = [0, (1 << 32) - 3000, n - 4000] + [int(x) for x in rng.integers(0, n - 4000, size=12)]
     for off in offs:
         got = a[off: off + 4000].cpu().numpy()
-        assert np.array_equal(got, m.awgn(u.state_at(16 + off), 0, 4000, fast=True)), off
+        assert np.array_equal(got, m.awgn(far.lutopt_state(u, m, 16 + off), 0, 4000, fast=True)), off
     del a
     torch.cuda.empty_cache()
 
@@ -201,7 +204,7 @@ def test_prefetch_hint_changes_nothing_but_timing(gpu, oracle):
     g = gpu.CLTGRNG(u)
     m = oracle.Lutopt(path=oracle.data_path(256))
     n = 3_000_000
-    ref = [m.awgn(u.state_at(16 + i * n), 0, 50_000, fast=True) for i in range(4)]
+    ref = [m.awgn(far.lutopt_state(u, m, 16 + i * n), 0, 50_000, fast=True) for i in range(4)]
     g.prefetch(n, first_step=16)
     outs = []
     for i in range(4):
@@ -215,7 +218,7 @@ def test_prefetch_hint_changes_nothing_but_timing(gpu, oracle):
     x = g.generate(1000, first_step=5).cpu().numpy()
     assert np.array_equal(x, m.awgn(1, 5, 1000, fast=True))
     y = g.generate(n, first_step=999)[:1000].cpu().numpy()
-    assert np.array_equal(y, m.awgn(u.state_at(999), 0, 1000, fast=True))
+    assert np.array_equal(y, m.awgn(far.lutopt_state(u, m, 999), 0, 1000, fast=True))
     # BER trials after a prefetch still see the right planes
     g.prefetch(n, first_step=16)
     t = gpu.Trial(nbits=50_000, amp=100, noise_var=8)
@@ -311,7 +314,7 @@ def test_n512_generated_kernel_matches_oracle(gpu, oracle, nsamples, first):
         exp = ((exp + 256) % 512) - 256
         assert got.dtype == np.int16 and np.array_equal(got[:len(exp)].astype(np.int64), exp)
         if nsamples > 20_000:            # the tail, from a jumped state
-            tail = m.states(u.state_at(first + nsamples - 5000), 0, 5000)
+            tail = m.states(far.lutopt_state(u, m, first + nsamples - 5000), 0, 5000)
             texp = ((m.clt_tree_bulk(tail).astype(np.int64) + 256) % 512) - 256
             assert np.array_equal(got[-5000:].astype(np.int64), texp)
 
@@ -336,7 +339,7 @@ def test_n512_stream_with_prefetch_hints(gpu, oracle):
     for s, o in enumerate(outs[:6]):
         assert torch.equal(o, d.generate(n, first_step=18 + s * n)), s
     assert torch.equal(outs[6], d.generate(n + 8, first_step=7))
-    st = m.states(u.state_at(18 + 2 * n), 0, 10_000)
+    st = m.states(far.lutopt_state(u, m, 18 + 2 * n), 0, 10_000)
     exp = ((m.clt_tree_bulk(st).astype(np.int64) + 256) % 512) - 256
     assert np.array_equal(outs[2][:10_000].cpu().numpy().astype(np.int64), exp)
 

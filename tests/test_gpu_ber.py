@@ -5,6 +5,8 @@ import numpy as np
 import pytest
 import torch
 
+import far
+
 pytestmark = pytest.mark.gpu
 
 
@@ -80,7 +82,8 @@ def test_generators_beyond_the_head_of_the_seeding(gpu, oracle, nbits, k, first)
 def test_sweep_multi_groups_on_one_device(gpu, oracle):
     """BBB_SHARD_GROUPS through bbb_ber_sweep_multi on one device (BASELINE configs[4]'s shape in small: 3 seeds x 4 points, the seeds
     as stretches of the one cycle 2^48 apart): every group one pass of its own noise stream, counters equal bbb_ber_trials' and,
-    for the first and the last seed, the oracle's (its jump to 2 x 2^48 is the product's own state_at: the oracle steps)."""
+    for the first and the last seed, the oracle's (its state 2 x 2^48 clocks on is the oracle's own jump, oracle/jump.py, which the product's
+    state_at must equal; tests/test_gpu_far.py prices all eight seeds of configs[4] this way)."""
     from basebandboard_amd import _lib
     from basebandboard_amd.channel import sweep_multi
     u = gpu.LUTOPT.shipped(256)
@@ -89,8 +92,8 @@ def test_sweep_multi_groups_on_one_device(gpu, oracle):
     assert got == gpu.run_trials(u, ts)
     m = oracle.Lutopt(path=oracle.data_path(256))
     assert got[:4] == [m.ber_trial(1, 31, 1, t.amp, 8, 16, 0, t.nbits) for t in ts[:4]]
-    far = u.state_at(2 << 48)                       # seed 2 = the reset state 2^49 clocks on
-    assert got[8:] == [m.ber_trial(far, 31, 1, t.amp, 8, 16, 0, t.nbits) for t in ts[8:]]
+    far2 = far.lutopt_state(u, m, 2 << 48)          # seed 2 = the reset state 2^49 clocks on
+    assert got[8:] == [m.ber_trial(far2, 31, 1, t.amp, 8, 16, 0, t.nbits) for t in ts[8:]]
 
 
 def test_grouped_trials_equal_individual_trials(gpu, oracle):
@@ -215,7 +218,7 @@ def test_cpp_caller_of_the_c_abi(gpu, oracle):
     row = [l.split() for l in r.stdout.splitlines() if l and not l.startswith("#")][0]
     amp = int(row[1])
     # seed d = the reset state advanced 2^48 d clocks (disjoint stretches of the one cycle), not init + d
-    seed1 = gpu.LUTOPT.shipped(256, init=0xa5).state_at(1 << 48)
+    seed1 = far.lutopt_state(gpu.LUTOPT.shipped(256, init=0xa5), m, 1 << 48)
     e = [m.ber_trial(s, 15, 1, amp, 7, 16, 0, 100_000) for s in (0xa5, seed1)]
     assert (int(row[2]), int(row[3])) == (e[0][0] + e[1][0], e[0][1] + e[1][1])
 
@@ -310,7 +313,7 @@ def test_cli_json_multi_and_awgn_modes(gpu, oracle):
     pts = [l for l in lines if "ebn0_db" in l]
     u = gpu.LUTOPT.shipped(256)
     for p in pts:
-        want = [m.ber_trial(u.state_at(s << 48) if s else 1, 31, 1, p["amp"], 8, 16, 0, 200_000) for s in range(3)]
+        want = [m.ber_trial(far.lutopt_state(u, m, s << 48), 31, 1, p["amp"], 8, 16, 0, 200_000) for s in range(3)]
         assert (p["bits"], p["errors"]) == (sum(b for b, _ in want), sum(e for _, e in want))
     summ = [l for l in lines if l.get("mode") == "ber_sweep"][0]
     assert summ["seeds"] == 3 and summ["shard"] == "groups" and summ["equals_single_device_counters"] is True and summ["total_bits"] == 3 * 3 * 200_000

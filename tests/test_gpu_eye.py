@@ -11,6 +11,7 @@ import torch
 import basebandboard_amd as bbb
 from basebandboard_amd.bitshaper import PRBSShaper, rcf_coefficients
 from basebandboard_amd.eye import BIT_SAMPLE0, EyeConfig, persistence
+import far
 from conftest import ROOT
 
 pytestmark = pytest.mark.gpu
@@ -31,7 +32,7 @@ def source_bits(k, pulser, m_lo, n, prbs_state=1):
     if pulser:
         return ((np.arange(m_lo, m_lo + n) & 255) == 0).astype(np.uint8)
     import oracle as O
-    s = bbb.PRBS(k, init=prbs_state, device=-1).state_at(m_lo) if m_lo else prbs_state
+    s = far.prbs_state(bbb.PRBS(k, init=prbs_state, device=-1), k, m_lo) if m_lo else prbs_state
     return O.prbs_bits(k, n, state=s)[0]
 
 

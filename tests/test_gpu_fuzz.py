@@ -5,6 +5,8 @@ import numpy as np
 import pytest
 import torch
 
+import far
+
 pytestmark = pytest.mark.gpu
 KS = (7, 9, 11, 15, 20, 23, 31)
 
@@ -18,7 +20,7 @@ def test_fuzz_prbs(gpu, oracle):
         init = int(rng.integers(1, 1 << k))
         p = gpu.PRBS(k, init=init)
         got = p.generate(nbits, first_bit=first).cpu().numpy().view(np.uint64)
-        exp, _ = oracle.prbs_packed(k, nbits, state=p.state_at(first), fast=True)
+        exp, _ = oracle.prbs_packed(k, nbits, state=far.prbs_state(p, k, first), fast=True)
         assert np.array_equal(got, exp), (k, nbits, first, init)
         buf = torch.from_numpy(got.view(np.int64).copy()).cuda()
         flips = np.unique(rng.integers(0, nbits, size=int(rng.integers(0, 50))))
@@ -37,7 +39,7 @@ def test_fuzz_awgn(gpu, oracle):
         init = int.from_bytes(rng.bytes(32), "little") | 1
         u = gpu.LUTOPT.shipped(256, init=init)
         got = gpu.CLTGRNG(u).generate(n, first_step=first).cpu().numpy()
-        exp = m.awgn(u.state_at(first), 0, n, fast=True)
+        exp = m.awgn(far.lutopt_state(u, m, first), 0, n, fast=True)
         assert np.array_equal(got, exp), (n, first)
 
 
@@ -95,4 +97,4 @@ def test_determinism_and_resume(gpu):
     whole = p.generate(64 * 100_000)
     pieces = [gpu.PRBS(23, init=0x1ABCD).generate(64 * 25_000, first_bit=64 * 25_000 * i) for i in range(4)]
     assert torch.equal(torch.cat(pieces), whole)
-    assert gpu.PRBS(23, init=p.state_at(64 * 50_000)).generate(64 * 50_000).equal(whole[50_000:])
+    assert gpu.PRBS(23, init=far.prbs_state(p, 23, 64 * 50_000)).generate(64 * 50_000).equal(whole[50_000:])

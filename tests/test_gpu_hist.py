@@ -8,6 +8,8 @@ import numpy as np
 import pytest
 import torch
 
+import far
+
 pytestmark = pytest.mark.gpu
 
 # the ragged list of the stream tests
@@ -80,7 +82,7 @@ def test_n512_histogram_equals_the_oracle_tree(gpu, oracle, nsamples, first):
         got = hist_of(gpu.CLTGRNG(u), nsamples, first)
         exp = np.zeros(512, dtype=np.int64)
         for off in range(0, nsamples, 1 << 20):
-            st = m.states(u.state_at(first + off), 0, min(1 << 20, nsamples - off))
+            st = m.states(far.lutopt_state(u, m, first + off), 0, min(1 << 20, nsamples - off))
             v = ((m.clt_tree_bulk(st).astype(np.int64) + 256) % 512) - 256
             exp += np.bincount(v + 256, minlength=512)
         assert got.shape == (512,) and np.array_equal(got, exp)
@@ -205,7 +207,7 @@ def test_fills_and_histograms_interleaved_on_one_handle(gpu, oracle, level):
         n = int(sizes[rng.integers(len(sizes))])
         what = int(rng.integers(4))
         first = pos if rng.integers(3) else int(rng.integers(1 << 30))
-        exp = m.awgn(u.state_at(first), 0, n, fast=True)
+        exp = m.awgn(far.lutopt_state(u, m, first), 0, n, fast=True)
         if what == 0:
             g.prefetch(n, first_step=first)
         if what <= 1:
@@ -215,7 +217,7 @@ def test_fills_and_histograms_interleaved_on_one_handle(gpu, oracle, level):
                 g.prefetch(n, first_step=first)           # an announcement meant for a fill, met by a histogram
             assert np.array_equal(hist_of(g, n, first), counts(exp, 256)), (step, n, first)
         pos = first + n
-    assert np.array_equal(g.generate(1 << 24, first_step=pos).cpu().numpy(), m.awgn(u.state_at(pos), 0, 1 << 24, fast=True))
+    assert np.array_equal(g.generate(1 << 24, first_step=pos).cpu().numpy(), m.awgn(far.lutopt_state(u, m, pos), 0, 1 << 24, fast=True))
 
 
 def test_table_driven_n256_handle(gpu, oracle):

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+import far
 from detector_geometry import default_chunk_words, form_of
 
 pytestmark = pytest.mark.gpu
@@ -34,10 +35,10 @@ def test_prbs_golden_prefix(gpu, golden_prbs, k):
 def test_prbs_fill_matches_oracle(gpu, oracle, k, nbits, first):
     p = gpu.PRBS(k)
     got = p.generate(nbits, first_bit=first).cpu().numpy().view(np.uint64)
-    s0 = p.state_at(first)
+    s0 = far.prbs_state(p, k, first)
     exp, s_end = oracle.prbs_packed(k, nbits, state=s0, fast=True)
     assert np.array_equal(got, exp)
-    assert p.state_at(first + nbits) == s_end
+    assert far.prbs_state(p, k, first + nbits) == s_end
 
 
 @pytest.mark.parametrize("k", (7, 20, 31))
@@ -135,7 +136,7 @@ def test_prbs31_beyond_2_pow_35_bits(gpu, oracle):
     rng = np.random.default_rng(1)
     for w in [0, (nbits // 64) - 40] + [int(x) for x in rng.integers(0, nbits // 64 - 40, size=10)]:
         got = buf[w: w + 32].cpu().numpy().view(np.uint64)
-        exp, _ = oracle.prbs_packed(31, 32 * 64, state=p.state_at(5 + 64 * w), fast=True)
+        exp, _ = oracle.prbs_packed(31, 32 * 64, state=far.prbs_state(p, 31, 5 + 64 * w), fast=True)
         assert np.array_equal(got, exp), w
     buf[12345] ^= 0x10
     buf[-1] ^= 1
@@ -161,7 +162,7 @@ def test_baseline_config3_full_size_with_error_mask(gpu, oracle):
     piece = 1 << 24                                            # 128 MiB of words at a time on the host
     for lo in range(0, buf2.numel(), piece):
         assert torch.equal(buf2[lo: lo + piece].cpu(), exp_t[lo: lo + piece]), f"PRBS-31 fill differs from the oracle in words [{lo}, {lo + piece})"
-    assert s_end == p.state_at(nbits)                         # and the LFSR state behind the last bit (the host's jump-ahead)
+    assert s_end == far.prbs_state(p, 31, nbits)                         # and the LFSR state behind the last bit (the host's jump-ahead)
     hinted = p.generate(nbits, will_read_back=True)
     assert torch.equal(hinted, buf2)
     del hinted, exp, exp_t
@@ -260,7 +261,7 @@ def test_fills_after_the_stream_of_an_earlier_fill_is_gone(gpu, oracle):
     for i in range(12):
         first = 1_000_003 * (i + 1)
         got = p.generate(100_000, first_bit=first).cpu().numpy().view(np.uint64)
-        exp, _ = oracle.prbs_packed(31, 100_000, state=p.state_at(first), fast=True)
+        exp, _ = oracle.prbs_packed(31, 100_000, state=far.prbs_state(p, 31, first), fast=True)
         assert np.array_equal(got, exp), i
     # and a plan shared between two live streams: the second user waits for the seed kernel by the plan's event
     s2 = torch.cuda.Stream()

@@ -8,7 +8,9 @@ import numpy as np
 import pytest
 import torch
 
+import oracle as O
 from conftest import GOLDEN
+from oracle import jump
 
 pytestmark = pytest.mark.gpu
 NS = (16, 32, 64, 128, 192, 256, 512)
@@ -50,6 +52,8 @@ def test_states_and_sample_stream_equal_reference_recur(gpu, ref_recur, n):
         u = gpu.LUTOPT.shipped(n, init=init)
         states = [int(h, 16) for h in ent["states_hex"]]
         assert [u.state_at(t + 1) for t in range(64)] == states
+        m = O.Lutopt(path=O.data_path(n))               # ... and the oracle's independent jump lands on the reference's states
+        assert [jump.lutopt_state(m, init, t) for t in (1, 2, 63, 64)] == [states[t - 1] for t in (1, 2, 63, 64)]
         if n % 32 == 0:
             w = u.generate_words(64).cpu().numpy().view(np.uint32).reshape(64, n // 32)
             got = [sum(int(x) << (32 * j) for j, x in enumerate(row)) for row in w]
@@ -117,7 +121,7 @@ def test_prbs_prefix_and_state_of_survey_appendix_b(gpu, k):
     p = gpu.PRBS(k)
     w = int(p.generate(64).cpu().numpy().view(np.uint64)[0])
     assert "".join(str((w >> t) & 1) for t in range(64)) == bits
-    assert p.state_at(64) == int(s, 16)
+    assert p.state_at(64) == int(s, 16) == jump.prbs_state(k, 1, 64)
     if k == 31:
         big = p.generate(10_000_000_000)
         assert int(big[:1].cpu().numpy().view(np.uint64)[0]) == w

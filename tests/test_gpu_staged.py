@@ -7,6 +7,8 @@ import numpy as np
 import pytest
 import torch
 
+import far
+
 pytestmark = pytest.mark.gpu
 
 BIG = 1 << 24          # fills of at least this many samples take the staged form
@@ -21,9 +23,9 @@ def test_staged_fill_equals_oracle_and_one_kernel_form(gpu, oracle):
     for n, first in ((BIG, 0), (BIG + 5, 16), (30_000_017, 12_345), (BIG - 16, 3)):       # the last one is below the threshold
         got = g.generate(n, first_step=first)
         snap = got.clone()                              # queued on the caller's stream right behind the fill
-        exp = m.awgn(u.state_at(first), 0, 300_000, fast=True)
+        exp = m.awgn(far.lutopt_state(u, m, first), 0, 300_000, fast=True)
         assert np.array_equal(snap[:300_000].cpu().numpy(), exp)
-        tail = m.awgn(u.state_at(first + n - 4096), 0, 4096, fast=True)
+        tail = m.awgn(far.lutopt_state(u, m, first + n - 4096), 0, 4096, fast=True)
         assert np.array_equal(snap[-4096:].cpu().numpy(), tail)
         assert torch.equal(snap, d.generate(n, first_step=first))
         assert torch.equal(got, snap)
@@ -155,7 +157,7 @@ def test_look_ahead_broken_chains(gpu, oracle, fills):
     torch.cuda.synchronize()
     for (cnt, first), got in zip(plan, outs):
         assert torch.equal(got, d.generate(cnt, first_step=first)), (cnt, first)
-        assert np.array_equal(got[:100_000].cpu().numpy(), m.awgn(u.state_at(first), 0, 100_000, fast=True))
+        assert np.array_equal(got[:100_000].cpu().numpy(), m.awgn(far.lutopt_state(u, m, first), 0, 100_000, fast=True))
 
 
 def test_look_ahead_interleaved_with_other_calls(gpu, oracle, golden_shaper):
@@ -272,9 +274,9 @@ def test_look_ahead_at_the_bench_size(gpu):
         d.generate(n, first_step=first(s), out=ref)
         assert torch.equal(buf, ref), s
     # per-rank stretches of bench.py: a position 2^48 steps in
-    far = (3 << 48) + 16
-    g.generate(n, first_step=far, out=buf)
-    d.generate(n, first_step=far, out=ref)
+    far_step = (3 << 48) + 16
+    g.generate(n, first_step=far_step, out=buf)
+    d.generate(n, first_step=far_step, out=ref)
     assert torch.equal(buf, ref)
 
 
@@ -396,7 +398,7 @@ def test_prefetch_survives_unrelated_fills_on_its_slot(gpu, oracle):
     for buf, first in ((x, 10_000_000_019), (y, 20_000_000_033)):
         got = buf.cpu().numpy()
         for off in (0, big // 2 - 77, big - 300_000):
-            assert np.array_equal(got[off:off + 300_000], m.awgn(u.state_at(first + off), 0, 300_000, fast=True)), (first, off)
+            assert np.array_equal(got[off:off + 300_000], m.awgn(far.lutopt_state(u, m, first + off), 0, 300_000, fast=True)), (first, off)
 
 
 def test_an_untaken_hint_does_not_race_the_next_one(gpu, oracle):
@@ -420,8 +422,8 @@ def test_an_untaken_hint_does_not_race_the_next_one(gpu, oracle):
         pos += n2
     torch.cuda.synchronize()
     for p, x in outs:
-        assert np.array_equal(x[:200_000].cpu().numpy(), m.awgn(u.state_at(p), 0, 200_000, fast=True)), p
-        tail = m.awgn(u.state_at(p + x.numel() - 4096), 0, 4096, fast=True)
+        assert np.array_equal(x[:200_000].cpu().numpy(), m.awgn(far.lutopt_state(u, m, p), 0, 200_000, fast=True)), p
+        tail = m.awgn(far.lutopt_state(u, m, p + x.numel() - 4096), 0, 4096, fast=True)
         assert np.array_equal(x[-4096:].cpu().numpy(), tail), p
 
 
@@ -443,8 +445,8 @@ def test_full_unit_byte_fill_equals_oracle_and_one_kernel_form(gpu, oracle, one_
     u.set_staged(True)
     got = gpu.CLTGRNG(u).generate(N144, first_step=16)
     assert torch.equal(got, one_kernel_144)
-    assert np.array_equal(got[:4096].cpu().numpy(), m.awgn(u.state_at(16), 0, 4096, fast=True))
-    assert np.array_equal(got[-4096:].cpu().numpy(), m.awgn(u.state_at(16 + N144 - 4096), 0, 4096, fast=True))
+    assert np.array_equal(got[:4096].cpu().numpy(), m.awgn(far.lutopt_state(u, m, 16), 0, 4096, fast=True))
+    assert np.array_equal(got[-4096:].cpu().numpy(), m.awgn(far.lutopt_state(u, m, 16 + N144 - 4096), 0, 4096, fast=True))
 
 
 def test_full_unit_look_ahead_window_starts_inside_a_segment(gpu, one_kernel_144):

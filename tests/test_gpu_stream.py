@@ -7,6 +7,8 @@ import numpy as np
 import pytest
 import torch
 
+import far
+
 pytestmark = pytest.mark.gpu
 
 BIG = 1 << 24
@@ -56,10 +58,9 @@ def test_stream_survives_a_broken_sequence(gpu, oracle):
     ref = m.awgn(1, 16, 3 * n, fast=True)
     for i, x in enumerate((a, b, c)):
         assert np.array_equal(x.cpu().numpy(), ref[i * n:(i + 1) * n]), i
-    far = m.awgn(u.state_at(5_000_000_000), 0, 400_000, fast=True)
-    assert np.array_equal(d[:400_000].cpu().numpy(), far)
-    assert np.array_equal(e[:300_000].cpu().numpy(), m.awgn(u.state_at(5_000_000_000 + n), 0, 300_000, fast=True))
-    assert np.array_equal(other[:200_000].cpu().numpy(), m.awgn(u.state_at(7_000_000_001), 0, 200_000, fast=True))
+    assert np.array_equal(d[:400_000].cpu().numpy(), m.awgn(far.lutopt_state(u, m, 5_000_000_000), 0, 400_000, fast=True))
+    assert np.array_equal(e[:300_000].cpu().numpy(), m.awgn(far.lutopt_state(u, m, 5_000_000_000 + n), 0, 300_000, fast=True))
+    assert np.array_equal(other[:200_000].cpu().numpy(), m.awgn(far.lutopt_state(u, m, 7_000_000_001), 0, 200_000, fast=True))
     assert np.array_equal(w.cpu().numpy().view(np.uint32), m.words_u32(1, 3, 500))
 
 
@@ -107,10 +108,10 @@ def test_stream_on_other_orders(gpu, oracle, k):
     for p in parts:
         got = p.cpu().numpy().astype(np.int64)
         if k == 32:
-            exp = m.awgn(u.state_at(pos), 0, p.numel()).astype(np.int64)
+            exp = m.awgn(far.lutopt_state(u, m, pos), 0, p.numel()).astype(np.int64)
         else:
             cnt = min(p.numel(), 20_000)
-            exp = ((m.clt_tree_bulk(m.states(u.state_at(pos), 0, cnt)).astype(np.int64) + 256) % 512) - 256
+            exp = ((m.clt_tree_bulk(m.states(far.lutopt_state(u, m, pos), 0, cnt)).astype(np.int64) + 256) % 512) - 256
             got = got[:cnt]
         assert np.array_equal(got, exp)
         pos += p.numel()
@@ -130,7 +131,7 @@ def test_waveform_stream_equals_the_plain_calls(gpu, oracle, golden_shaper):
         parts.append(st.next())
         assert st.tell() == 100 + 5 * n + 1_000_003
         st.seek(3_000_000_017)
-        far = st.next()
+        far_part = st.next()
         torch.cuda.synchronize()
     assert x.urng is not None and gpu._lib.lib().bbb_tx_stream_close(None) == gpu._lib.BBB_OK
     pos = 100
@@ -138,7 +139,7 @@ def test_waveform_stream_equals_the_plain_calls(gpu, oracle, golden_shaper):
         ref = y.generate(p.numel(), first_sample=pos, stream_on=False)
         assert torch.equal(p, ref), i
         pos += p.numel()
-    assert torch.equal(far, y.generate(n, first_sample=3_000_000_017, stream_on=False))
+    assert torch.equal(far_part, y.generate(n, first_sample=3_000_000_017, stream_on=False))
     m = oracle.Lutopt(path=oracle.data_path(256))
     exp = oracle.tx(m, 1, golden_shaper["rcf_coeffs"][16], 31, 100_000, first_sample=100 + n, noise_var=8, warmup=16)
     assert np.array_equal(parts[1][:100_000].cpu().numpy(), exp)
@@ -146,7 +147,7 @@ def test_waveform_stream_equals_the_plain_calls(gpu, oracle, golden_shaper):
 
 
 def u_state(m, step, x):
-    return x.urng.state_at(step)
+    return far.lutopt_state(x.urng, m, step)
 
 
 def test_waveform_stream_refuses_a_second_stream_and_restores_the_level(gpu):

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+import far
 from conftest import GOLDEN
 
 pytestmark = pytest.mark.gpu
@@ -42,7 +43,7 @@ def test_shaper_matches_oracle(gpu, oracle, golden_shaper, k, setsel, n, first):
         bit0 = (first - 17) // 8 - 7       # first data bit the window needs
         p = gpu.PRBS(k)
         exp = oracle.shaper(golden_shaper["rcf_coeffs"][setsel], k, n, first_sample=first - 8 * bit0,
-                            prbs_state=p.state_at(bit0))
+                            prbs_state=far.prbs_state(p, k, bit0))
     else:
         exp = oracle.shaper(golden_shaper["rcf_coeffs"][setsel], k, n, first_sample=first)
     assert np.array_equal(got, exp)
@@ -74,6 +75,35 @@ def test_tx_short_windows_at_the_start(gpu, oracle, golden_shaper, n, first):
     m = oracle.Lutopt(path=oracle.data_path(256))
     exp = oracle.tx(m, 1, golden_shaper["rcf_coeffs"][16], 31, n, first_sample=first, noise_var=8, warmup=16)
     assert np.array_equal(got, exp)
+
+
+def oracle_tx_far(oracle, x, coeffs, n, first, warmup=16):
+    """oracle.tx for a window the oracle cannot walk to: its PRBS starts at the first data bit the window needs and its
+    noise generator at the step that goes with it, both states from the oracle's own jump (tests/far.py)."""
+    m = oracle.Lutopt(path=oracle.data_path(256))
+    bit0 = (first - 17) // 8 - 7
+    return oracle.tx(m, far.lutopt_state(x.urng, m, warmup + 8 * bit0), coeffs, x.prbs.k, n, first_sample=first - 8 * bit0,
+                     prbs_state=far.prbs_state(x.prbs, x.prbs.k, bit0), noise_var=x.noise_var, warmup=0)
+
+
+@pytest.mark.parametrize("n,first", [(300_007, (3 << 48) + 1)])
+def test_tx_with_noise_at_a_far_first_sample(gpu, oracle, golden_shaper, n, first):
+    x = gpu.TX(31, 1, 0, 16, 1, 8)
+    got = x.generate(n, first_sample=first).cpu().numpy()
+    assert np.array_equal(got, oracle_tx_far(oracle, x, golden_shaper["rcf_coeffs"][16], n, first))
+
+
+def test_tx_stream_seek_to_a_far_sample(gpu, oracle, golden_shaper):
+    x = gpu.TX(31, 1, 0, 16, 1, 8)
+    n, pos = (1 << 24) + 4096, (2 << 48) + 9
+    with x.stream(n, first_sample=100) as st:
+        st.seek(pos)
+        parts = [st.next(), st.next()]
+        assert st.tell() == pos + 2 * n
+        torch.cuda.synchronize()
+    for i, p in enumerate(parts):
+        assert np.array_equal(p[:100_000].cpu().numpy(), oracle_tx_far(oracle, x, golden_shaper["rcf_coeffs"][16], 100_000, pos + i * n)), i
+        assert np.array_equal(p[-4096:].cpu().numpy(), oracle_tx_far(oracle, x, golden_shaper["rcf_coeffs"][16], 4096, pos + (i + 1) * n - 4096)), i
 
 
 def test_tx_large_and_statistics(gpu, oracle, golden_shaper):
