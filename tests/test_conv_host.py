@@ -16,6 +16,7 @@ from basebandboard_amd import _lib
 from conftest import ROOT
 
 import fir_model
+import grid
 import conv_model as M
 
 G171 = (0o171, 0o133)
@@ -401,3 +402,60 @@ def test_closed_loop_counts(name):
     print(name, r)
     assert r == M.LOOP_COUNTS[name]
     assert r["soft"] < r["hard"] < r["channel"]
+
+
+# ---- past one pass of the decoder's grid ---------------------------------------------------------------------------------------
+# The decode kernel's workgroups take ceil(nblocks / wpg) groups of windows, at most 16 per compute unit at a time
+# (tests/grid.py).  These records make workgroup 0 take three turns of that loop and leave the last pass ragged, at the
+# smallest geometry there is.  tests/test_gpu_conv.py runs them on the GPU; the expected bits are bbb_conv_model_host's,
+# which is held to the model here on three stretches of the same record (windows do not depend on one another).
+# Out of reach at this cost: the encoder's grid is capped at 2^20 workgroups of 256 words, 2^34 transmitted bits a pass.
+MULTIPASS_GEOM = (8, 8, 8)
+MULTIPASS = {"K7_soft": dict(K=7, gens=G171, period=1, keep=None, wpg=4, hard=False),
+             "K3_hard_punctured": dict(K=3, gens=(7, 5, 7), period=3, keep=(0b101, 0b011, 0b110), wpg=64, hard=True)}
+
+
+def multipass_record(name, ncus):
+    """(code, values, hard, nblocks, wpg) of a multi-pass case on a device of ncus compute units: random data through
+    bbb_conv_encode_host; soft values carry noise of sigma 40 on +-64, hard bits are wrong one time in 16."""
+    c = MULTIPASS[name]
+    B = MULTIPASS_GEOM[0]
+    code = M.Code(c["K"], c["gens"], c["period"], c["keep"], init_state=1)
+    nblocks = c["wpg"] * grid.passes(grid.CONV_DECODE, ncus=ncus) - 1
+    nsteps = B * nblocks - 3
+    rng = np.random.default_rng(70 + c["K"])
+    tx, nout, _ = _encode_host(code, rng.integers(0, 2, nsteps))
+    tx = tx[:nout]
+    if c["hard"]:
+        vals = (tx ^ (rng.integers(0, 16, nout) == 0)).astype(np.int64)
+    else:
+        vals = ((2 * tx.astype(np.int64) - 1) * 64 + np.rint(rng.normal(0, 40, nout))).astype(np.int16)
+    assert -(-nblocks // c["wpg"]) == grid.passes(grid.CONV_DECODE, ncus=ncus) and nblocks % c["wpg"] and nsteps % B
+    return code, vals, c["hard"], nblocks, c["wpg"]
+
+
+def multipass_expected(name, ncus):
+    """(code, values, hard, nblocks, expected bits): the whole record from bbb_conv_model_host, held to the model on the groups
+    around the start of pass 2, on groups inside pass 3 and on the ragged end."""
+    code, vals, hard, nblocks, wpg = multipass_record(name, ncus)
+    B, W, D = MULTIPASS_GEOM
+    want, _ = _model_host(code, vals, 0, B=B, W=W, D=D, hard=hard)
+    g = grid.CONV_DECODE * ncus                                          # groups in a pass
+    for glo, ghi in ((g - 2, g + 2), (2 * g + 1, 2 * g + 4), (-(-nblocks // wpg) - 3, None)):
+        first = glo * wpg * B
+        nb = M.nbefore_wanted(code, first, B, W, D)
+        lo = M.idx(code, first) - nb
+        if ghi is None:
+            got, _ = M.run(code, vals[lo:], nb, first, True, B, W, D, hard)
+            assert first + len(got) == len(want)
+        else:
+            got, _ = M.run(code, vals[lo:M.idx(code, ghi * wpg * B + D)], nb, first, False, B, W, D, hard)
+            assert len(got) == (ghi - glo) * wpg * B
+        assert np.array_equal(got, want[first:first + len(got)]), (name, glo)
+    return code, vals, hard, nblocks, want
+
+
+@pytest.mark.parametrize("name", sorted(MULTIPASS))
+def test_multipass_host_model_equals_the_model_on_stretches(name):
+    code, vals, hard, nblocks, want = multipass_expected(name, 256)
+    assert len(want) == 8 * nblocks - 3 and 0 < want.mean() < 1

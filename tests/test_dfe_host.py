@@ -14,6 +14,7 @@ from basebandboard_amd import _lib, equalizer
 from conftest import ROOT
 
 import fir_model
+import grid
 import dfe_model as M
 
 
@@ -309,3 +310,47 @@ def test_closed_loop_on_the_oracle_waveform(oracle):
     assert e_lin > 0 and e_dfe < e_lin
     # the raw slicer at the pulse's peak, for scale
     assert M.loop_errors(fir_model.decisions(y, [1], 8, (17 + int(np.abs(h).argmax())) % 8), ref)[0] > e_lin
+
+
+# ---- past one pass of the grids ----------------------------------------------------------------------------------------------------
+# The region kernel takes a region a turn and the repair kernel a region that started wrong, each at most 8 workgroups per
+# compute unit at a time (tests/grid.py).  At 16 symbols a region these records are short enough for the model itself, so
+# tests/test_gpu_dfe.py holds the GPU to tests/dfe_model.py over the whole of them; here the model says that they do what they
+# are for.
+MULTIPASS_REGION = 16
+MULTIPASS_NOISY = dict(fb=[280, 100, -50], warmup=3)
+MULTIPASS_ZERO = dict(taps=[3, -2, 1], fb=[5], warmup=7)
+
+
+def multipass_noisy(spb, ncus):
+    """(samples, taps, fb, phase) of 2 * 8 * ncus + 5 regions, the last cut short: two-level data with an echo of 0.7 one symbol
+    late and noise, through a moving average of the symbol's samples."""
+    nsym = MULTIPASS_REGION * (grid.passes(grid.DFE, ncus=ncus) - 1) + 9
+    rng = np.random.default_rng(60 + spb)
+    d = rng.choice([-400, 400], nsym)
+    sym = d + np.concatenate([[0], (d[:-1] * 0.7).astype(np.int64)])
+    x = np.repeat(sym, spb) // spb + rng.normal(0, 150 / spb, nsym * spb).astype(np.int64)
+    return x.astype(np.int16), [1] * spb, MULTIPASS_NOISY["fb"], spb - 1
+
+
+def multipass_zero(spb, ncus):
+    """All-zero samples under fb = {5}: every decision is the inverse of the last, no warm-up proves a start, and with an odd
+    warm-up the speculation from state 0 fails for every other region.  2 * (2 * 8 * ncus + 5) + 3 regions, so that the regions
+    to repair are more than two passes of the repair kernel's grid."""
+    nreg = 2 * grid.passes(grid.DFE, ncus=ncus) + 3
+    return np.zeros((MULTIPASS_REGION * (nreg - 1) + 5) * spb, dtype=np.int16)
+
+
+@pytest.mark.parametrize("spb", (1, 2))
+def test_multipass_records_in_the_model(spb):
+    ncus = 256
+    x, taps, fb, phase = multipass_noisy(spb, ncus)
+    a = fir_model.acc(x, taps)[phase::spb]
+    st = M.replay(a, fb, 0, False, 5, MULTIPASS_REGION, MULTIPASS_NOISY["warmup"])
+    assert st["regions"] == grid.passes(grid.DFE, ncus=ncus) and st["symbols"] % MULTIPASS_REGION and 0 < st["repaired"] <= st["not_proven"] < st["regions"]
+    bits = M.decide(a, fb, 0, False, 5)[0]
+    assert 0.4 < bits.mean() < 0.6
+    z = multipass_zero(spb, ncus)
+    a = fir_model.acc(z, MULTIPASS_ZERO["taps"])[spb - 1::spb]
+    st = M.replay(a, MULTIPASS_ZERO["fb"], 0, False, 0, MULTIPASS_REGION, MULTIPASS_ZERO["warmup"])
+    assert st["not_proven"] == st["regions"] - 1 and st["repaired"] > 2 * grid.DFE * ncus

@@ -14,6 +14,7 @@ import basebandboard_amd as bbb
 from basebandboard_amd import _lib
 from conftest import ROOT
 
+import grid
 import framesync_model as M
 
 GUARD = 0xA5A5A5A5A5A5A5A5
@@ -444,3 +445,113 @@ def test_closed_loop_counts():
     assert got["blind_failed"] == got["blind_codewords"] == 64                    # without sync every codeword fails
     got.pop("pos")
     assert got == M.SYNC_LOOP_COUNTS
+
+
+# ---- past one pass of the grids ----------------------------------------------------------------------------------------------------
+# The search pass takes tiles of 16384 bits, extract and attach a word a lane, each at most 16 workgroups of 256 lanes per
+# compute unit at a time (tests/grid.py).  Extract writes the payload alone, (F - M) / F of the stream, so two passes of the
+# search tiles can never be two passes of extract: the stream is three passes and five tiles long, which takes search and
+# attach through a fourth turn and extract through a third.  tests/test_gpu_framesync.py runs it on the GPU.  The expected
+# records are bbb_framesync_model_host's, held to the model here on three stretches, each entered in LOCK at a record of the
+# host model's whose predecessor was no miss; the expected bytes are the payloads that were attached, which
+# bbb_frame_extract_host is held to here as well.
+MULTIPASS_CFG = M.Cfg(M.CCSDS_MARKER, 32, 200, 1, 4, 2, 1, rand=M.CCSDS_RAND)
+MULTIPASS_JUNK, MULTIPASS_TILE = 1237, 16384
+MULTIPASS_GAPS = ((-1, 2), (60, 63), (1, 3))         # pass 2 (from the tile before it on), pass 3 and the ragged pass 4
+
+
+def multipass_stream(ncus):
+    """(packed words, nbits, payload bytes, framed words, nframes, which frames are inverted): frames of 200 bits from
+    bbb_frame_attach_host behind 1237 junk bits, a ragged tail of 77 bits behind the last tile and part of a frame at the end.  Every seventh marker has one wrong bit;
+    every 1000th frame's marker is missed (flywheeled); every 3000th and its successor are missed: the lock is lost and found
+    again two frames on; the frames of forty tiles from the middle of pass 3's second tile on are inverted; and in every later
+    pass of the search every marker of some whole tiles is missed (MULTIPASS_GAPS, in tiles from the pass's first), so that
+    the chain searches through tiles that the search pass wrote on a workgroup's second, third and fourth turn."""
+    c, J, T = MULTIPASS_CFG, MULTIPASS_JUNK, MULTIPASS_TILE
+    G = grid.FRAMESYNC * ncus
+    nbits = T * grid.passes(grid.FRAMESYNC, k=3, ncus=ncus) + 77
+    nframes = (nbits - J - 150) // c.F
+    rng = np.random.default_rng(97)
+    pay = rng.integers(0, 256, nframes * c.payload_bytes, dtype=np.uint8)
+    framed = np.zeros((nframes * c.F + 63) // 64, dtype=np.uint64)
+    assert _lib.lib().bbb_frame_attach_host(C.c_void_p(pay.ctypes.data), nframes, C.byref(cfg_of(c)), C.c_void_p(framed.ctypes.data)) == 0
+    bits = np.empty(nbits, dtype=np.uint8)
+    bits[:J] = rng.integers(0, 2, J, dtype=np.uint8)
+    bits[J:J + nframes * c.F] = np.unpackbits(framed.view(np.uint8), bitorder="little")[:nframes * c.F]
+    bits[J + nframes * c.F:] = rng.integers(0, 2, nbits - J - nframes * c.F, dtype=np.uint8)
+    fr = np.arange(nframes, dtype=np.int64)
+    bits[J + c.F * fr[3::7] + 5] ^= 1
+    gaps = [np.arange(-(-((p * G + lo) * T - J) // c.F), ((p * G + hi) * T - J) // c.F) for p, (lo, hi) in enumerate(MULTIPASS_GAPS, 1)]
+    missed = np.unique(np.concatenate([fr[500::1000], fr[1700::3000], fr[1701::3000]] + gaps))
+    for b in (0, 6, 11, 17, 23, 30):
+        bits[J + c.F * missed + b] ^= 1
+    i0, i1 = ((2 * G + 1) * T + T // 2 - J) // c.F, ((2 * G + 41) * T - J) // c.F
+    bits[J + c.F * i0:J + c.F * i1] ^= 1
+    return M.pack(bits), nbits, pay, framed, nframes, (fr >= i0) & (fr < i1)
+
+
+def multipass_expected(ncus):
+    """(words, nbits, payload, framed words, nframes, inverted, pos, meta, state words) with the records of
+    bbb_framesync_model_host, held to the model on the tiles around the start of pass 2 (a gap of missed markers among them),
+    on tiles inside pass 3 (where the inverted stretch begins) and on the ragged pass 4."""
+    c, T = MULTIPASS_CFG, MULTIPASS_TILE
+    words, nbits, pay, framed, nframes, inv = multipass_stream(ncus)
+    mf = nbits // c.F + 2
+    st = np.zeros(8, dtype=np.uint64)
+    pos, meta = np.zeros(mf, dtype=np.uint64), np.zeros(mf, dtype=np.uint16)
+    rc = _lib.lib().bbb_framesync_model_host(C.c_void_p(words.ctypes.data), nbits, 0, 1, C.byref(cfg_of(c)), C.c_void_p(st.ctypes.data),
+                                             C.c_void_p(pos.ctypes.data), C.c_void_p(meta.ctypes.data), mf)
+    assert rc == 0, _lib.lib().bbb_last_error_detail()
+    n = int(st[0]) >> 32
+    pos, meta, st = pos[:n].astype(np.int64), meta[:n], st.tolist()
+    G = grid.FRAMESYNC * ncus
+    for lo, hi in (((G - 3) * T, (G + 4) * T), ((2 * G + 1) * T, (2 * G + 3) * T), (3 * G * T, None)):
+        k = int(np.searchsorted(pos, lo))
+        while meta[k - 1] >> 9 & 1 or meta[k] >> 10 & 1:              # entered in LOCK with no miss carried
+            k += 1
+        a, b = int(pos[k]), nbits if hi is None else hi
+        s = M.new_state(a)
+        s.update(mode=M.LOCK, pol=int(meta[k]) >> 8 & 1)
+        piece = _bits_of(words, a, b)
+        gpos, gmeta, s = M.run(c, piece, a, hi is None, s)
+        assert len(gpos) >= (b - a - 3 * T) // c.F - 8 and gpos == pos[k:k + len(gpos)].tolist() and gmeta == meta[k:k + len(gpos)].tolist(), (lo, k)
+        if hi is None:
+            assert k + len(gpos) == n and M.words(s)[1] == st[1] and M.words(s)[0] & 0xFFFFFFFF == st[0] & 0xFFFFFFFF
+        else:
+            assert s["losses"] >= 1 and s["acquisitions"] >= 1, "the stretch holds no loss of lock"
+    return words, nbits, pay, framed, nframes, inv, pos, meta, st
+
+
+def multipass_payloads(pay, inv, pos, meta):
+    """What extract returns for the records: every one is a frame that was attached, so its payload, complemented where the
+    record's polarity is not the frame's (a frame flywheeled over where the inverted stretch begins or ends)."""
+    c = MULTIPASS_CFG
+    idx, rem = np.divmod(pos - MULTIPASS_JUNK, c.F)
+    assert not rem.any() and idx[-1] == len(inv) - 1
+    wrong_pol = ((meta >> 8 & 1) != inv[idx]).astype(np.uint8)
+    assert 0 < int(wrong_pol.sum()) <= 2
+    return (pay.reshape(len(inv), c.payload_bytes)[idx] ^ (0xFF * wrong_pol)[:, None]).reshape(-1)
+
+
+def _bits_of(words, a, b):
+    """The bits [a, b) of packed words."""
+    w0, w1 = a // 64, (b + 63) // 64
+    return np.unpackbits(words[w0:w1].view(np.uint8), bitorder="little")[a - 64 * w0:b - 64 * w0]
+
+
+def test_multipass_host_model_equals_the_model_on_stretches():
+    c = MULTIPASS_CFG
+    words, nbits, pay, framed, nframes, inv, pos, meta, st = multipass_expected(256)
+    lanes = grid.FRAMESYNC * 256 * 256                                   # a pass of extract or attach, a word a lane
+    assert nbits > 3 * lanes * 64 and len(framed) > 2 * lanes and len(pos) * c.payload_bytes // 8 + 1 > 2 * lanes
+    # what the machine made of it: the junk passed over, both polarities, losses every 3000 frames, all but the lost frames found
+    assert pos[0] == MULTIPASS_JUNK and st[5] >= nframes // 3000 + 3 and st[4] == st[5] + 1 and st[3] >= nframes // 1000
+    want = multipass_payloads(pay, inv, pos, meta)
+    out = np.full(len(want) + 8, 0xA5, dtype=np.uint8)
+    state = np.array(st, dtype=np.uint64)
+    p, m = pos.astype(np.uint64), np.ascontiguousarray(meta)
+    assert _lib.lib().bbb_frame_extract_host(C.c_void_p(words.ctypes.data), nbits, 0, C.c_void_p(p.ctypes.data), C.c_void_p(m.ctypes.data),
+                                             C.c_void_p(state.ctypes.data), len(pos), C.byref(cfg_of(c)), C.c_void_p(out.ctypes.data)) == 0
+    assert np.array_equal(out[:len(want)], want) and (out[len(want):] == 0xA5).all()
+    assert 0 < int((meta >> 8 & 1).sum()) < len(meta) and nframes - 2 * st[5] - 8 * MULTIPASS_TILE // c.F - 4 <= len(pos) <= nframes
+    assert st[0] & 0xFF == M.LOCK and nframes // 7 - st[3] - 2 * st[5] <= st[7] <= nframes // 7 + 1    # (a missed marker's wrong bits are not counted)

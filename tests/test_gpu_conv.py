@@ -1,7 +1,10 @@
 """bbb_conv_encode and bbb_conv_decode on the GPU, bit for bit against tests/conv_model.py: every constraint length, two and
 three coded bits, punctured periods, small and default windows, records around the block sizes, soft and hard values, calls
 that start inside a block with more and less history than wanted, calls that are not final, a stream cut at random points,
-the tie rules, the metrics' bound, termination, and the closed loop of tests/test_conv_host.py."""
+the tie rules, the metrics' bound, termination, more than two passes of the decoder's grid, and the closed loop of tests/test_conv_host.py.
+
+Out of reach at a test's cost: more than one pass of the encoder's grid, which is capped at 2^20 workgroups of one output word a
+thread (2^34 transmitted bits a pass)."""
 import ctypes as C
 
 import numpy as np
@@ -9,7 +12,9 @@ import pytest
 import torch
 
 import fir_model
+import grid
 import conv_model as M
+import test_conv_host as H
 
 pytestmark = pytest.mark.gpu
 
@@ -289,6 +294,20 @@ def test_rx_count_errors_with_fec(gpu):
     assert rx.count_errors(xt, fec=cc) == (errors, n) and 0 < errors < int(uncoded.sum())
     assert rx.detect(xt, fec=cc)["errors"] == rx.prbsdet.run_stream(own, n2)["errors"]
     assert rx.count_errors(xt, rx_filter=gpu.FIR([1]), fec=cc) == (errors, n)           # the filter {1} is the plain slicer
+
+
+@pytest.mark.parametrize("name", sorted(H.MULTIPASS))
+def test_more_than_two_passes_of_the_grid(gpu, name):
+    """ceil(nblocks / wpg) = 2 * 16 * cus + 5 groups of windows at B = W = D = 8 (tests/test_conv_host.py builds the records and
+    holds bbb_conv_model_host, the expected bits here, to the model on three stretches): workgroup 0 takes three turns of its
+    loop over the groups, re-using the stage and the survivor words, and the last pass does not fill the grid.  The encoder's
+    loop is out of reach at this cost: its grid is capped at 2^20 workgroups of 256 words a pass."""
+    code, vals, hard, nblocks, want = H.multipass_expected(name, grid.cus())
+    B, W, D = H.MULTIPASS_GEOM
+    bits, stats = _decode(gpu, code, vals, B=B, W=W, D=D, hard=hard, in_off=3, bits_off=1)
+    bad = np.flatnonzero(bits != want)
+    assert len(bits) == len(want) and len(bad) == 0, f"{len(bad)} bits differ, the first at step {bad[0]} of {len(want)}"
+    assert stats == dict(windows=nblocks, steps=len(want))
 
 
 # ---- the closed loop ---------------------------------------------------------------------------------------------------

@@ -1,5 +1,6 @@
 """bbb_dfe_run on the GPU against tests/dfe_model.py: bits, soft values, the final state word and the counters of stats_dev, with
-regions and warm-ups set small through the call so that a short record has many regions, the speculation and the repair."""
+regions and warm-ups set small through the call so that a short record has many regions, the speculation and the repair, and more regions than two passes of
+the region and repair kernels' grids."""
 import ctypes as C
 
 import numpy as np
@@ -7,7 +8,9 @@ import pytest
 import torch
 
 import fir_model
+import grid
 import dfe_model as M
+import test_dfe_host as H
 
 pytestmark = pytest.mark.gpu
 
@@ -198,6 +201,23 @@ def test_ambiguous_stretch_across_every_boundary(gpu, spb):
     x = rng.choice([-500, 500], nsym * spb)
     x[(2 * region - 40) * spb:(2 * region + 40) * spb] = 0
     assert _check(gpu, x, 0, taps, [50], spb, phase, region=region, warmup=warmup)["not_proven"] == 1
+
+
+@pytest.mark.parametrize("spb", (1, 2))
+def test_more_than_two_passes_of_the_grids(gpu, spb):
+    """Regions of 16 symbols (tests/test_dfe_host.py builds the records), in the block form of one sample a symbol and in the
+    point form.  Noisy data over 2 * 8 * cus + 5 regions: a workgroup of the region kernel takes three regions, re-using the
+    image, the waves' totals and the gathered ends behind its loop's last barrier.  The all-zero record over twice as many:
+    the model repairs more regions than two passes of the repair kernel's grid, which then loops as well."""
+    x, taps, fb, phase = H.multipass_noisy(spb, grid.cus())
+    st = _check(gpu, x, 0, taps, fb, spb, phase, region=H.MULTIPASS_REGION, warmup=H.MULTIPASS_NOISY["warmup"], state=5, shift=1,
+                in_off=3, bits_off=1, soft_off=1)
+    assert st["regions"] == grid.passes(grid.DFE) and 0 < st["repaired"] <= st["not_proven"]
+    z, Z = H.multipass_zero(spb, grid.cus()), H.MULTIPASS_ZERO
+    want = M.replay(np.zeros(len(z) // spb, dtype=np.int64), Z["fb"], 0, False, 0, H.MULTIPASS_REGION, Z["warmup"])
+    assert want["repaired"] > 2 * grid.DFE * grid.cus(), "the model does not repair more than two passes of regions"
+    st = _check(gpu, z, 0, Z["taps"], Z["fb"], spb, spb - 1, region=H.MULTIPASS_REGION, warmup=Z["warmup"], soft=np.int32, in_off=1)
+    assert st == want
 
 
 def test_noisy_data_with_the_default_geometry(gpu):

@@ -15,6 +15,7 @@ from basebandboard_amd.bitshaper import PRBSShaper
 from basebandboard_amd.eye import capture_eye
 from conftest import ROOT
 import fir_model as M
+import grid
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda", 0)
@@ -35,8 +36,8 @@ def dev(a):
 
 
 def grid_stride():
-    """Input samples one pass of the grid covers (8 workgroups per compute unit)."""
-    return T * 8 * torch.cuda.get_device_properties(0).multi_processor_count
+    """Input samples one pass of the grid covers (tests/grid.py has the workgroups per compute unit)."""
+    return T * grid.FIR * grid.cus()
 
 
 def taps_at_limit(rng, ntaps):

@@ -3,7 +3,7 @@ of tests/test_framesync_host.py through the C ABI (records, the count, all state
 buffer between guard words and the scratch of exactly the plan's size, stream lengths around the search pass's tile, a wave's and
 a lane's share, markers that straddle a word, a wave's share and a tile at every offset, frames on tile boundaries, two calls
 that add to one state, the error flag, max_frames overflow, the adversarial streams, extract and attach against their host forms
-at every bit offset, and the Python classes: FrameSync, FrameSyncStream cut at random word multiples, and Concatenated(sync=)
+at every bit offset, a stream of more than two passes of every kernel's grid, and the Python classes: FrameSync, FrameSyncStream cut at random word multiples, and Concatenated(sync=)
 through RX.count_errors on the closed loop of tests/test_framesync_host.py."""
 import ctypes as C
 
@@ -11,7 +11,9 @@ import numpy as np
 import pytest
 import torch
 
+import grid
 import framesync_model as M
+import test_framesync_host as H
 
 pytestmark = pytest.mark.gpu
 
@@ -249,6 +251,47 @@ def test_extract_and_attach_equal_their_host_forms(gpu, pb):
         dev = _extract_gpu(c, M.pack(bits), len(bits), 0, pos, meta, 3, 3)
         host = _extract_host(c, M.pack(bits), len(bits), 0, pos, meta, 3, 3)
         assert np.array_equal(dev[:3 * pb], host[:3 * pb]) and not dev[2 * pb:3 * pb].any() and np.array_equal(dev[:2 * pb], pay[:2 * pb])
+
+
+def test_more_than_two_passes_of_the_grids(gpu):
+    """One stream of three passes and five tiles of the search pass and a ragged tail (tests/test_framesync_host.py builds it and
+    holds bbb_framesync_model_host, the expected records here, to the model on three stretches): frames of 200 bits behind junk,
+    wrong marker bits, flywheeled frames, a loss of lock every 3000 frames and at the tile where pass 2 begins, forty tiles
+    inverted.  Attach on the GPU against the host's words, the search and chain passes against the host model's positions, meta
+    and eight state words, extract against the payloads that were attached: search and attach take a fourth turn of their
+    loops, extract (the payload is 168 / 200 of the stream) a third."""
+    from basebandboard_amd import _lib
+    c = H.MULTIPASS_CFG
+    words, nbits, pay, framed, nframes, inv, wpos, wmeta, wst = H.multipass_expected(grid.cus())
+    lanes = grid.FRAMESYNC * grid.cus() * 256
+    assert nbits > 3 * lanes * 64 and len(framed) > 2 * lanes and len(wpos) * c.payload_bytes // 8 + 1 > 2 * lanes
+    stream = C.c_void_p(torch.cuda.current_stream(0).cuda_stream)
+    src = torch.from_numpy(pay).to("cuda:0")
+    s = Slab(out=len(framed))
+    rc = _lib.lib().bbb_frame_attach(C.c_void_p(src.data_ptr()), nframes, C.byref(cfg_of(c)), s.ptr("out"), 0, stream)
+    assert rc == 0, _lib.lib().bbb_last_error_detail()
+    assert np.array_equal(s.read()["out"], framed), "attach differs from bbb_frame_attach_host"
+    del s, src
+    mf = nbits // c.F + 2
+    plan = _plan(c, nbits)
+    s = Slab(inp=len(words), state=8, pos=mf, meta=(mf + 3) // 4, scratch=plan.scratch_bytes // 8, out=(mf * c.payload_bytes + 7) // 8)
+    s.put("inp", words)
+    s.put("state", np.zeros(8, dtype=np.uint64))
+    rc = _lib.lib().bbb_framesync_run(s.ptr("inp"), nbits, 0, 1, C.byref(cfg_of(c)), s.ptr("state"), s.ptr("pos"), s.ptr("meta"), mf, s.ptr("scratch"), 0, stream)
+    assert rc == 0, _lib.lib().bbb_last_error_detail()
+    rc = _lib.lib().bbb_frame_extract(s.ptr("inp"), nbits, 0, s.ptr("pos"), s.ptr("meta"), s.ptr("state"), mf, C.byref(cfg_of(c)), s.ptr("out"), 0, stream)
+    assert rc == 0, _lib.lib().bbb_last_error_detail()
+    got = s.read()
+    n = len(wpos)
+    assert got["state"].tolist() == wst, (got["state"].tolist(), wst)
+    assert np.array_equal(got["inp"], words), "the input was written"
+    assert np.array_equal(got["pos"][:n].astype(np.int64), wpos), int(np.flatnonzero(got["pos"][:n].astype(np.int64) != wpos)[0])
+    assert np.array_equal(got["meta"].view(np.uint16)[:n], wmeta), int(np.flatnonzero(got["meta"].view(np.uint16)[:n] != wmeta)[0])
+    assert (got["pos"][n:] == np.uint64(GUARD & (2 ** 64 - 1))).all() and (got["meta"].view(np.uint16)[n:] == 0xA5A5).all(), "records beyond the count were written"
+    out = got["out"].view(np.uint8)
+    want = H.multipass_payloads(pay, inv, wpos, wmeta)
+    assert np.array_equal(out[:len(want)], want), int(np.flatnonzero(out[:len(want)] != want)[0])
+    assert (out[len(want):] == 0xA5).all(), "bytes beyond the count's payloads were written"
 
 
 def _dev(bits):

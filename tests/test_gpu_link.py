@@ -1,7 +1,7 @@
 """The filtered link on the GPU, bit-exact: bbb_link_sweep_* / LinkSweep against the raw analysers (identity filter), against
 the numpy model of tests/link_model.py on the oracle's waveform, against the product's own composition (TX.generate ->
 FIR.slice / FIR.filter -> capture_eye), over thresholds in units of acc, cuts of a range, the start of the stream, a range
-far out, many settings at once, the handle left as it was, and the C++ example."""
+far out, more than two passes of the kernel's grid, many settings at once, the handle left as it was, and the C++ example."""
 import functools
 import json
 import subprocess
@@ -16,6 +16,7 @@ from basebandboard_amd.eye import BIT_SAMPLE0, EyeConfig, capture_eye
 from basebandboard_amd.txsweep import TxSetting
 from conftest import ROOT
 
+import grid
 import link_model
 from test_gpu_eye import CONFIGS, make_tx, source_bits, tx_taps, u64
 
@@ -235,6 +236,28 @@ def test_far_out(gpu):
     x = make_tx(**kw).generate(count, first_sample=x0).cpu().numpy()
     tub, h = model(kw, fir, delay, first, n, eye=eye, x=x, x0=x0)
     assert np.array_equal(cnt[0], tub) and np.array_equal(hist[0], h)
+
+
+# ---- 7b. more than two passes of the grid ----------------------------------------------------------------------------------------
+
+def test_more_than_two_passes_of_the_grid(gpu):
+    """2048 * (2 * 8 * cus + 5) + 77 samples behind the moving average from an odd first sample, in one chunk: the kernel's grid is
+    at most 8 workgroups a compute unit (tests/grid.py), so workgroup 0 takes three or more steps of 2048, alternating its two
+    LDS images with the inputs of the next step in flight, and the last pass is ragged.  One ber_sweep and one eye + bathtub call
+    against the model on TX.generate's output, as test_far_out takes it."""
+    kw, fir, delay, first = dict(k=7, nv=9, shape=16), bbb.FIR(MA), 2, 12_345
+    n = 2048 * grid.passes(grid.LINK) + 77
+    eye = EyeConfig(ncols=64, shift=4, col_origin=BIT_SAMPLE0)
+    x0, count = link_model.wave_range(first, n, len(MA), delay)
+    x = make_tx(**kw).generate(count, first_sample=x0).cpu().numpy()
+    tub, h = model(kw, fir, delay, first, n, threshold=7, eye=eye, x=x, x0=x0)
+    assert h.sum() == n and tub[:, 1].sum() > 0 and tub[:, 0].sum() == n
+    sweep = u64(make_tx(k=7, nv=3).ber_sweep(n, noise_vars=[9], shape_sels=[16], first_sample=first, rx_filter=fir, delay=delay, threshold=7))
+    assert sweep.shape == (1, 1, 8, 2) and np.array_equal(sweep[0, 0], tub), (sweep[0, 0].tolist(), tub.tolist())
+    tx = make_tx(**kw)
+    cnt, hist = run_link(tx, fir, delay, first, n, [own_setting(tx, 7)], eye)
+    assert np.array_equal(cnt[0], tub), (cnt[0].tolist(), tub.tolist())
+    assert np.array_equal(hist[0], h)
 
 
 # ---- 8. many settings ------------------------------------------------------------------------------------------------

@@ -1,6 +1,6 @@
 """bbb_mlse_run on the GPU, bit for bit against tests/mlse_model.py: every memory and decimation, small and default windows,
 records around the block sizes, calls that start inside a block, calls that are not final, a stream cut at random points, the
-tie rules, the metrics' bound, and the closed loop of tests/test_mlse_host.py."""
+tie rules, the metrics' bound, more than two passes of the grid, and the closed loop of tests/test_mlse_host.py."""
 import ctypes as C
 
 import numpy as np
@@ -8,8 +8,10 @@ import pytest
 import torch
 
 import fir_model
+import grid
 import dfe_model
 import mlse_model as M
+import test_mlse_host as H
 
 pytestmark = pytest.mark.gpu
 
@@ -172,6 +174,20 @@ def test_a_capture_cut_at_random_points_equals_one_call(gpu, spb, geom):
     assert d.stats()["symbols"] == 2 * nsym
     # the same cuts in the model
     assert np.array_equal(M.stream(x, taps, g, spb, cuts, spb - 1, 2, B=geom[0], W=geom[1], D=geom[2]), want)
+
+
+@pytest.mark.parametrize("name", sorted(H.MULTIPASS))
+def test_more_than_two_passes_of_the_grid(gpu, name):
+    """ceil(nblocks / wpg) = 2 * 16 * cus + 5 groups of windows (tests/test_mlse_host.py builds the records and holds
+    bbb_mlse_model_host, the expected bits here, to the model on three stretches): workgroup 0 takes three turns of its loop over
+    the groups, re-using the image, the span and the survivor words, and the last pass does not fill the grid.  Sixteen and two
+    states at B = W = D = 8 in the 256-thread kernel, and B + W + D = 512 at four states, which mlse_shape gives the 64-thread
+    kernel with two steps in flight."""
+    x, g, (B, W, D), nblocks, want = H.multipass_expected(name, grid.cus())
+    bits, stats = _call(gpu, x, 0, H.MULTIPASS_TAPS, g, 1, 0, H.MULTIPASS_SHIFT, init=1, B=B, W=W, D=D, in_off=3, bits_off=1)
+    bad = np.flatnonzero(bits != want)
+    assert len(bits) == len(want) and len(bad) == 0, f"{len(bad)} bits differ, the first at symbol {bad[0]} of {len(want)}"
+    assert stats == dict(windows=nblocks, symbols=len(want))
 
 
 def test_closed_loop_counts_equal_the_cpu(gpu, oracle):

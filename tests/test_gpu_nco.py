@@ -1,7 +1,10 @@
 """The numerically controlled oscillator on the GPU, compared exactly with the numpy model of gateware/bbb/nco.py
 (tests/nco_model.py): the reference's known answer, NCOTest's defaults, every mix of buffer and constant inputs, sizes around
 every boundary of the kernels, split invariance, the registers, seek, streams, spectra through RX.spectrum, NCO.acf and the
-C++ example."""
+C++ example.
+
+Out of reach: more than one pass of the grid in the fm tile kernels.  bbb_nco_run hands them chunks of 2^24 samples, which
+never hold more tiles than their grid has workgroups (tests/grid.py has the kernels that do loop)."""
 import json
 import subprocess
 

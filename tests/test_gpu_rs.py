@@ -2,15 +2,20 @@
 first roots, root spacings, 2..32 parity symbols, lengths around the lane and tile sizes, depths 1, 3 and 8, every error
 pattern), the statistics added to over two calls, frame counts that fill and do not fill a workgroup's four frames, buffers
 that start 0, 1, 3 and 15 bytes off alignment between guard bytes, the outputs that may be left out, a record with clean,
-corrected and failed codewords in one workgroup, the encoder against bbb_rs_encode_host, and the Python classes: ReedSolomon,
-RSStream cut at random points, and Concatenated through RX.count_errors on the closed loop of tests/test_rs_host.py."""
+corrected and failed codewords in one workgroup, more than two passes of the decoder's grid, the encoder against bbb_rs_encode_host, and the Python classes: ReedSolomon,
+RSStream cut at random points, and Concatenated through RX.count_errors on the closed loop of tests/test_rs_host.py.
+
+Out of reach at a test's cost: more than one pass of the encoder's grid, which is capped at 2^16 workgroups of one codeword a
+thread (2^24 codewords a pass)."""
 import ctypes as C
 
 import numpy as np
 import pytest
 import torch
 
+import grid
 import rs_model as M
+import test_rs_host as H
 
 pytestmark = pytest.mark.gpu
 
@@ -123,6 +128,27 @@ def test_clean_corrected_and_failed_in_one_workgroup(gpu):
     failed = np.repeat(c["nerr"].reshape(4, 4) == M.FAILED, 223, axis=0).reshape(4, 223, 4)      # [frame, symbol, codeword]
     got, recv = data.reshape(4, 223, 4), c["recv"].reshape(4, 255, 4)[:, :223, :]
     assert np.array_equal(got[failed], recv[failed])                                          # a failed codeword's data pass through
+
+
+@pytest.mark.parametrize("which", (7, 3), ids=("short", "ccsds"))
+def test_more_than_two_passes_of_the_grid(gpu, counted, which):
+    """The seven-frame records repeated to 4 * (2 * 16 * cus + 5) + 1 frames, neither a multiple of 7 nor of 4: workgroup 0 takes
+    three turns of its loop over the groups of four frames, re-using the stage and the waves' scratch and carrying its counters,
+    every pattern meets every slot of a group, and the last group holds one frame.  Frames are independent, so the expected data
+    and nerr are the model's, tiled, and the statistics the model's times the whole tiles plus the remainder's
+    (tests/test_rs_host.py holds that arithmetic to bbb_rs_model_host).  The encoder's loop is out of reach at this cost: its
+    grid is capped at 2^16 workgroups of 256 codewords a pass."""
+    c = counted[which]
+    code, nframes = c["code"], H.multipass_frames(grid.cus())
+    assert c["nframes"] == 7 and nframes % 7 and nframes % 4
+    recv, out, want_nerr, want_stats = H.tile_case(c, nframes)
+    stats = torch.tensor([5, 4, 3, 2, 1], dtype=torch.int64, device="cuda:0")
+    data, nerr = _decode(gpu, code, recv, nframes, 3, 1, stats=stats)
+    assert np.array_equal(nerr, want_nerr), int(np.flatnonzero(nerr != want_nerr)[0])
+    assert np.array_equal(data, out), int(np.flatnonzero(data != out)[0])
+    assert stats.cpu().tolist() == [a + b for a, b in zip(want_stats, (5, 4, 3, 2, 1))]
+    data, nerr = _decode(gpu, code, recv, nframes, 3, 1, want_nerr=False)
+    assert np.array_equal(data, out) and len(nerr) == 0
 
 
 def test_nothing_is_written_for_no_frames(gpu):

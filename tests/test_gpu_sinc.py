@@ -15,6 +15,7 @@ from basebandboard_amd import _lib
 from basebandboard_amd.eye import EyeConfig, capture_eye
 from conftest import GOLDEN, ROOT
 import sinc_model as M
+import grid
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda", 0)
@@ -32,8 +33,8 @@ def dev(a):
 
 
 def grid_stride():
-    """Input samples one pass of the grid covers (8 workgroups per compute unit)."""
-    return BLOCK * 8 * torch.cuda.get_device_properties(0).multi_processor_count
+    """Input samples one pass of the grid covers (tests/grid.py has the workgroups per compute unit)."""
+    return BLOCK * grid.SINC * grid.cus()
 
 
 def check(x, shift=0, out_dtype=None, nbefore=0, **kw):

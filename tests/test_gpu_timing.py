@@ -1,6 +1,6 @@
 """bbb_timing_run on the GPU against tests/timing_model.py, bit for bit: bits, soft values, the phase of every block, the state
 words, the counters of stats_dev and nbits_dev, with guard words around every output and the pointers off 16-byte alignment
-where the ABI allows it."""
+where the ABI allows it; and records of more than two passes of every kernel's grid."""
 import ctypes as C
 
 import numpy as np
@@ -8,7 +8,9 @@ import pytest
 import torch
 
 import fir_model
+import grid
 import timing_model as M
+import test_timing_host as H
 
 pytestmark = pytest.mark.gpu
 
@@ -201,6 +203,19 @@ def test_wrap_down_in_block_0_reads_the_sample_in_front_of_the_call(gpu):
     assert n1 == L and n2 == one["nbits"] - L and one["wraps"][1] == -1
     assert np.array_equal(soft[:n2].cpu().numpy(), one["soft"][L:]) and ph.cpu().tolist() == one["phases"][1:].tolist()
     assert tuple(int(v) for v in st.cpu().numpy().view(np.uint64)) == one["state"]
+
+
+@pytest.mark.parametrize("name", sorted(H.MULTIPASS))
+def test_more_than_two_passes_of_the_grids(gpu, name):
+    """The drifting-noise records of tests/test_timing_host.py, which holds bbb_timing_model_host, the expected values here, to the
+    model on three stretches.  small_blocks (8 symbols of 3 samples, the smallest block there is): 2 * 8 * cus + 5 tiles and more
+    chunks than that, so the metric, chunk, walk and gather kernels all take a third turn with a prefetched tile, their last pass
+    is ragged, and a chain thread owns several chunks.  long_blocks (1024 symbols of 8 samples): 8 * cus + 3 blocks of four tiles,
+    two passes of the metric kernel's sums over a block's tiles and five of the gather kernel's."""
+    x, taps, P, L, chunk, want = H.multipass_expected(name, grid.cus())
+    assert want["stats"][1] > 8 and want["stats"][2] >= 1 and want["stats"][3] >= 1, "the record does not move and wrap both ways"
+    got = _call(x, 0, P, taps, L, H.MULTIPASS_H, H.MULTIPASS_THRESHOLD, True, M.ACQUIRE, chunk, shift=H.MULTIPASS_SHIFT, in_off=3)
+    _same(got, want, name)
 
 
 def _unpack(words, n):

@@ -16,6 +16,7 @@ from basebandboard_amd import _lib, equalizer
 from conftest import ROOT
 
 import fir_model
+import grid
 import dfe_model
 import mlse_model as M
 
@@ -323,3 +324,80 @@ def test_closed_loop_on_the_oracle_waveform(oracle):
     assert r["dfe"][0] >= 50 and r["mlse"][0] < r["dfe"][0]
     # the channels that were tried first leave the DFE without an error: the reason for the added noise
     assert dfe_model.LOOP_DFE_ERRORS == 0
+
+
+# ---- past one pass of the detector's grid ------------------------------------------------------------------------------------
+# The kernel's workgroups take ceil(nblocks / wpg) groups of windows, at most 16 per compute unit at a time (tests/grid.py).
+# These records make workgroup 0 take three turns of that loop and leave the last pass ragged.  tests/test_gpu_mlse.py runs
+# them on the GPU; the expected bits are bbb_mlse_model_host's, held to the model here on three stretches of the same record
+# (windows do not depend on one another).
+MULTIPASS_TAPS, MULTIPASS_SHIFT = [2, 1, -1], 1
+MULTIPASS = {"NS16": dict(g=[50, -30, 20, 12, -9], geom=(8, 8, 8), threads=256),
+             "NS2": dict(g=[60, 45], geom=(8, 8, 8), threads=256),
+             # B + W + D = 512.  At sixteen states no geometry leaves the 256-thread kernel (4624 + 4 * 4096 + 2 * (16 * 510 + 2)
+             # bytes fit); four states are the most that reach the 64-thread one, with the fewest windows a workgroup
+             "threads64": dict(g=[60, 45, -20], geom=(448, 32, 32), threads=64)}
+
+
+def mlse_shape(ns, B, W, D):
+    """(threads, windows per workgroup, LDS bytes) of mlse_kernels.hip's mlse_shape: the FIR image of (256 + 2048) / 2 + 4 words,
+    B + W + D survivor words a wave, two bytes a symbol of the span; the workgroup halves until 40 KiB hold it."""
+    for threads in (256, 128, 64):
+        wpg = threads // ns
+        nbytes = (4624 + threads // 64 * (B + W + D) * 8 + 2 * (wpg * B + W + D) + 15) & ~15
+        if nbytes <= 40 * 1024:
+            break
+    return threads, wpg, nbytes
+
+
+def multipass_record(name, ncus):
+    """(samples int16, g, (B, W, D), nblocks, wpg) at one sample a symbol: +-1 data through the target plus uniform noise."""
+    c = MULTIPASS[name]
+    g, (B, W, D) = c["g"], c["geom"]
+    threads, wpg, _ = mlse_shape(1 << (len(g) - 1), B, W, D)
+    assert threads == c["threads"]
+    nblocks = wpg * grid.passes(grid.MLSE, ncus=ncus) - 1
+    n = B * nblocks - 3
+    rng = np.random.default_rng(80 + len(g))
+    d = rng.integers(0, 2, n + len(g), dtype=np.int16) * 2 - 1
+    x = rng.integers(-40, 41, n, dtype=np.int16)
+    for i, v in enumerate(g):
+        x += np.int16(v) * d[len(g) - i:len(g) - i + n]
+    return x, g, (B, W, D), nblocks, wpg
+
+
+def multipass_expected(name, ncus):
+    """(samples, g, geometry, nblocks, expected bits): the whole record from bbb_mlse_model_host, held to the model on the groups
+    around the start of pass 2, on groups inside pass 3 and on the ragged end."""
+    x, g, (B, W, D), nblocks, wpg = multipass_record(name, ncus)
+    taps, shift = MULTIPASS_TAPS, MULTIPASS_SHIFT
+    want, _ = _model_host(x, 0, _cfg(taps, g, 1, 0, shift, 1, B, W, D))
+    per = grid.MLSE * ncus                                               # groups in a pass
+    for glo, ghi in ((per - 1, per + 1), (2 * per + 1, 2 * per + 3), (-(-nblocks // wpg) - 2, None)):
+        first = glo * wpg * B
+        nb = M.nbefore_wanted(first, 1, len(taps), 0, B, W, D)
+        if ghi is None:
+            got, _ = M.run(x[first:], taps, g, 1, 0, shift, x[first - nb:first], first, True, 1, B, W, D)
+            assert first + len(got) == len(want)
+        else:
+            got, _ = M.run(x[first:ghi * wpg * B + D], taps, g, 1, 0, shift, x[first - nb:first], first, False, 1, B, W, D)
+            assert len(got) == (ghi - glo) * wpg * B
+        assert np.array_equal(got, want[first:first + len(got)]), (name, glo)
+    return x, g, (B, W, D), nblocks, want
+
+
+def test_mlse_shape_restated():
+    """The shapes the multi-pass cases rely on: 16 and 128 windows a workgroup of 256 threads at B = W = D = 8, and the long
+    geometry at four states, which exceeds the 40 KiB target at 256 and at 128 threads and runs the 64-thread kernel."""
+    assert mlse_shape(16, 8, 8, 8)[:2] == (256, 16) and mlse_shape(2, 8, 8, 8)[:2] == (256, 128)
+    B, W, D = MULTIPASS["threads64"]["geom"]
+    assert B + W + D == 512
+    at128 = (4624 + 2 * 512 * 8 + 2 * (128 // 4 * B + W + D) + 15) & ~15
+    assert at128 == 41616 > 40 * 1024 and mlse_shape(4, B, W, D) == (64, 16, 4624 + 4096 + 2 * (16 * 448 + 64))
+    assert mlse_shape(16, 510, 1, 1)[0] == mlse_shape(16, 448, 32, 32)[0] == 256   # sixteen states never leave 256 threads
+
+
+@pytest.mark.parametrize("name", sorted(MULTIPASS))
+def test_multipass_host_model_equals_the_model_on_stretches(name):
+    x, g, (B, W, D), nblocks, want = multipass_expected(name, 256)
+    assert len(want) == B * nblocks - 3 and 0 < want.mean() < 1

@@ -14,6 +14,7 @@ import basebandboard_amd as bbb
 from basebandboard_amd import _lib
 from conftest import ROOT
 
+import grid
 import rs_model as M
 
 GUARD = 0xA5
@@ -323,3 +324,43 @@ def test_closed_loop_counts():
         assert r["channel"] > r["viterbi"] > 0
     assert deep["failed"] == 0 and deep["data_bits"] == 0 and 0 < deep["worst"] <= 16
     assert flat["failed"] >= 1
+
+
+# ---- past one pass of the decoder's grid ---------------------------------------------------------------------------------------
+# The decode kernel's workgroups take four frames a turn, at most 16 workgroups per compute unit at a time (tests/grid.py).
+# Frames are independent by definition, so a record of more than two passes is a short record's frames repeated and its
+# expected values are the model's, tiled.  tests/test_gpu_rs.py runs such records on the GPU.
+# Out of reach at this cost: the encoder's grid is capped at 2^16 workgroups of 256 codewords, 2^24 codewords a pass.
+
+def multipass_frames(ncus):
+    """4 * (2 * 16 * ncus + 5) + 1 frames: workgroup 0 takes three turns, the last pass is ragged and its last group holds one
+    frame."""
+    return 4 * grid.passes(grid.RS_DECODE, ncus=ncus) + 1
+
+
+def tile_case(c, nframes):
+    """The case c (tests/rs_model.py, make_case) with its received frames repeated up to nframes: (recv, out, nerr, stats), the
+    statistics those of c times the whole tiles plus the model's for the frames of the remainder."""
+    code, nf = c["code"], c["nframes"]
+    whole, rest = divmod(nframes, nf)
+
+    def rep(a, per):
+        a = np.asarray(a).reshape(nf, per)
+        return np.concatenate([np.tile(a, (whole, 1)), a[:rest]]).reshape(-1)
+    recv, out, nerr = rep(c["recv"], code.frame_bytes), rep(c["out"], code.data_bytes), rep(c["nerr"], code.depth)
+    tail = M.decode(code, c["recv"][:rest * code.frame_bytes])[2] if rest else [0] * 5
+    return recv, out, nerr, [whole * a + b for a, b in zip(c["stats"], tail)]
+
+
+@pytest.mark.parametrize("code,ncus", ((M.Code(40, 36, 0x12B, 1, 11, 3), 256), (M.ccsds(4), 8)), ids=("short", "ccsds"))
+def test_tiled_records_equal_the_host_model(code, ncus):
+    """The tiling arithmetic of the multi-pass records, against bbb_rs_model_host over the whole tiled record."""
+    c = M.make_case(code, np.random.default_rng(45), 7, M.PATTERNS)
+    nframes = multipass_frames(ncus)
+    assert nframes % 7 and nframes % 4 == 1
+    recv, out, nerr, stats = tile_case(c, nframes)
+    assert len(recv) == nframes * code.frame_bytes and np.array_equal(recv[-code.frame_bytes:], c["recv"][(nframes - 1) % 7 * code.frame_bytes:][:code.frame_bytes])
+    data, ne, st = _model_host(code, recv, nframes)
+    assert np.array_equal(data, out) and np.array_equal(ne, nerr) and st == stats
+    assert stats[0] == nframes * code.depth and stats[1] == int((nerr == 0).sum()) and stats[2] == int((nerr == M.FAILED).sum())
+    assert stats[3] == int(nerr[nerr != M.FAILED].sum())

@@ -14,6 +14,7 @@ from basebandboard_amd import _lib
 from conftest import ROOT
 
 import fir_model
+import grid
 import timing_model as M
 
 
@@ -314,3 +315,66 @@ def test_closed_loop_on_the_oracle_waveform(oracle, step):
     assert (down, up) == ((M.LOOP_WRAPS, 0) if step > 65536 else (0, M.LOOP_WRAPS))
     assert r["nbits"] == L["n"] // L["P"] + down - up
     assert abs(ppm - (65536 - step) / 65536 * 1e6) < 15.0
+
+
+# ---- past one pass of the grids ----------------------------------------------------------------------------------------------------
+# The metric and gather kernels take tiles of 2048 samples, the chunk and walk kernels chunks of blocks, each at most 8
+# workgroups per compute unit at a time (tests/grid.py).  These records take all four past two passes and leave the last pass
+# ragged; tests/test_gpu_timing.py runs them on the GPU.  The expected values are bbb_timing_model_host's, held to the model here
+# on three stretches of blocks, each entered with the state the host model left in front of it (the phase of the block before
+# and the bits emitted so far, which the phases of whole blocks give).  spb = 2 is refused by bbb_timing_run, so the smallest
+# block is 8 symbols of 3 samples, 85 of them a tile.
+MULTIPASS = {"small_blocks": dict(P=3, L=8), "long_blocks": dict(P=8, L=1024)}
+MULTIPASS_H, MULTIPASS_THRESHOLD, MULTIPASS_SHIFT = 4, 11, 2
+
+
+def multipass_record(name, ncus):
+    """(samples, taps, P, L, chunk_blocks, nblocks) of the drifting-noise record (timing_model.drift_record).
+    small_blocks: 2 * 8 * ncus + 5 tiles, the last with 7 blocks of which the last is cut short, and chunks of as many blocks as
+    make more chunks than tiles, so that a chain thread's share is several chunks.
+    long_blocks: 8 * ncus + 3 blocks of four tiles each, the last block cut short, one block a chunk."""
+    P, L = MULTIPASS[name]["P"], MULTIPASS[name]["L"]
+    LP = L * P
+    rng = np.random.default_rng(90 + P)
+    if name == "small_blocks":
+        per_tile, ntiles = 2048 // LP, grid.passes(grid.TIMING, ncus=ncus)
+        nblocks = per_tile * (ntiles - 1) + 7
+        n, chunk = (nblocks - 1) * LP + 11, nblocks // ntiles
+        assert -(-nblocks // per_tile) == ntiles and -(-nblocks // chunk) > 2 * grid.TIMING * ncus
+    else:
+        assert LP > 2048
+        nblocks, chunk = grid.passes(grid.TIMING, k=1, extra=3, ncus=ncus), 1
+        n = (nblocks - 1) * LP + 4099
+    return M.drift_record(rng, P, L, n).astype(np.int16), M.phase_taps(rng, 7, P), P, L, chunk, nblocks
+
+
+def multipass_expected(name, ncus):
+    """(samples, taps, P, L, chunk_blocks, the host model's dict): the whole record from bbb_timing_model_host, held to the model on
+    the blocks around the start of pass 2 of the metric kernel, on blocks inside pass 3 (of the gather kernel's tiles, where a
+    block is several) and on the ragged end.  The record moves and wraps both ways."""
+    x, taps, P, L, chunk, nblocks = multipass_record(name, ncus)
+    h, thr, shift, LP = MULTIPASS_H, MULTIPASS_THRESHOLD, MULTIPASS_SHIFT, L * P
+    want = _model_host(x, 0, _cfg(P, taps, L, h, thr, True, M.ACQUIRE, chunk, shift=shift))
+    assert want["stats"][0] == nblocks and want["stats"][1] > 8 and want["stats"][2] >= 1 and want["stats"][3] >= 1, want["stats"]
+    ph = want["phases"].astype(np.int64)
+    d = np.diff(ph)
+    wraps = np.concatenate([[0], (d == 1 - P).astype(np.int64) - (d == P - 1)])      # P - 1 -> 0 is up, 0 -> P - 1 is down
+    per = grid.TIMING * ncus * (2048 // LP if LP <= 2048 else 1)                     # blocks in a pass of the metric kernel
+    third = 2 * per + 3 if LP <= 2048 else 2 * grid.TIMING * ncus * 2048 // LP + 1   # ... and a block of the gather kernel's pass 3
+    for j0, j1 in ((per - 2, per + 2), (third, third + 3), (nblocks - 3, None)):
+        off = L * j0 - int(wraps[:j0].sum())
+        r = M.run(x[j0 * LP:j1 * LP if j1 else None], P, taps, L, h, thr, True, before=x[j0 * LP - len(taps):j0 * LP],
+                  state=(M.LOCKED | int(ph[j0 - 1]), off), final=j1 is None, shift=shift)
+        assert np.array_equal(r["phases"], want["phases"][j0:j1]), (name, j0)
+        assert np.array_equal(r["bits"], want["bits"][off:off + r["nbits"]]) and np.array_equal(r["soft"], want["soft"][off:off + r["nbits"]]), (name, j0)
+        if j1 is None:
+            assert r["state"] == want["state"] and off + r["nbits"] == want["nbits"]
+        else:
+            assert r["nbits"] == L * (j1 - j0) - int(wraps[j0:j1].sum())
+    return x, taps, P, L, chunk, want
+
+
+@pytest.mark.parametrize("name", sorted(MULTIPASS))
+def test_multipass_host_model_equals_the_model_on_stretches(name):
+    x, taps, P, L, chunk, want = multipass_expected(name, 256)
+    assert len(want["phases"]) == -(-len(x) // (L * P))
