@@ -30,6 +30,7 @@ SYMBOLS = [
     "bbb_dfe_run", "bbb_dfe_geometry", "bbb_dfe_model_host",
     "bbb_mlse_plan", "bbb_mlse_run", "bbb_mlse_model_host",
     "bbb_timing_plan", "bbb_timing_run", "bbb_timing_model_host",
+    "bbb_carrier_plan", "bbb_carrier_run", "bbb_carrier_model_host",
     "bbb_conv_plan", "bbb_conv_encode", "bbb_conv_encode_host", "bbb_conv_decode", "bbb_conv_model_host",
     "bbb_rs_encode", "bbb_rs_encode_host", "bbb_rs_decode", "bbb_rs_model_host",
     "bbb_framesync_plan", "bbb_framesync_run", "bbb_frame_extract", "bbb_frame_attach", "bbb_framesync_model_host",
@@ -120,6 +121,12 @@ class MlseCfg(C.Structure):
     """bbb_mlse_cfg"""
     _fields_ = [("ff", FirCfg), ("mem", C.c_uint32), ("g", C.c_int32 * 5), ("init_state", C.c_uint32),
                 ("block_symbols", C.c_uint32), ("warmup_symbols", C.c_uint32), ("lookahead_symbols", C.c_uint32)]
+
+
+class CarrierCfg(C.Structure):
+    """bbb_carrier_cfg"""
+    _fields_ = [("block_pairs", C.c_uint32), ("init_phase", C.c_uint32), ("threshold", C.c_int32), ("strict", C.c_uint32),
+                ("chunk_blocks", C.c_uint32)]
 
 
 class TimingCfg(C.Structure):
@@ -328,6 +335,9 @@ def lib():
     l.bbb_timing_plan.argtypes = [C.POINTER(TimingCfg), u64, i32, u64p, u64p, u64p, u64p]
     l.bbb_timing_run.argtypes = [vp, u64, C.c_uint32, i32, C.POINTER(TimingCfg), vp, vp, vp, vp, vp, vp, i32, vp]
     l.bbb_timing_model_host.argtypes = [vp, u64, C.c_uint32, i32, C.POINTER(TimingCfg), vp, vp, vp, vp, vp, u64p]
+    l.bbb_carrier_plan.argtypes = [C.POINTER(CarrierCfg), u64, i32, u64p, u64p]
+    l.bbb_carrier_run.argtypes = [vp, u64, i32, C.POINTER(CarrierCfg), vp, vp, vp, vp, vp, vp, i32, vp]
+    l.bbb_carrier_model_host.argtypes = [vp, u64, i32, C.POINTER(CarrierCfg), vp, vp, vp, vp, vp, vp]
     l.bbb_conv_plan.argtypes = [C.POINTER(ConvCfg), u64, u64, i32, u64p, u64p, u64p]
     l.bbb_conv_encode.argtypes = [vp, u64, u64, C.POINTER(ConvCfg), vp, vp, u64p, i32, vp]
     l.bbb_conv_encode_host.argtypes = [vp, u64, u64, C.POINTER(ConvCfg), C.POINTER(C.c_uint32), vp, u64p]

@@ -63,15 +63,20 @@ class DDC:
         assert got.value == n
         return out
 
-    def iq(self, samples, first_sample=0, nbefore=0, out_dtype=torch.int16, out=None):
+    def iq(self, samples, first_sample=0, nbefore=0, out_dtype=torch.int16, out=None, carrier=None):
         """[nout, 2] (I, Q) of an int16 CUDA tensor (bbb_ddc_run).  The first `nbefore` elements of `samples` are the
         record's earlier samples, as in FIR.filter, and samples[nbefore] has the absolute number `first_sample`.  out_dtype
-        torch.int16 saturates, torch.int32 never needs to.  Asynchronous on the current torch stream."""
+        torch.int16 saturates, torch.int32 never needs to.  Asynchronous on the current torch stream.
+        carrier (a carrier.CarrierRecovery; int16 only, excludes out): the pairs go through carrier.derotate, and what
+        comes back are the pairs turned back by the recovered carrier phase, the data axis on I."""
+        if carrier is not None and (out is not None or out_dtype != torch.int16):
+            raise ValueError("carrier takes int16 pairs and excludes out")
         if out is not None:
             out_dtype = out.dtype
         if out_dtype not in _MODE:
             raise ValueError("out_dtype must be torch.int16 or torch.int32")
-        return self._run(samples, first_sample, nbefore, _MODE[out_dtype], out)
+        pairs = self._run(samples, first_sample, nbefore, _MODE[out_dtype], out)
+        return pairs if carrier is None else carrier.derotate(pairs)
 
     def polar(self, samples, first_sample=0, nbefore=0, out=None):
         """(mag uint16 [nout], phase int16 [nout]): views of one interleaved [nout, 2] int16 tensor (`out` when given)."""

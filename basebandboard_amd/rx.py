@@ -173,10 +173,10 @@ class RX:
         from .equalizer import rx_pulse_response
         return rx_pulse_response(samples, bits, self.samples_per_bit, origin, nlags, first_sample, bit0)
 
-    def downconvert(self, samples, ddc, **kw):
+    def downconvert(self, samples, ddc, carrier=None, **kw):
         """Baseband [nout, 2] (I, Q) of an int16 CUDA capture at a carrier: ddc.iq(samples, **kw) of a ddc.DDC (first_sample,
-        nbefore, out_dtype, out)."""
-        return ddc.iq(samples, **kw)
+        nbefore, out_dtype, out).  carrier (a carrier.CarrierRecovery): the pairs turned back by the recovered carrier phase."""
+        return ddc.iq(samples, carrier=carrier, **kw)
 
     def phase_search(self, samples, stride=None, strict=False, interpolate=False, shift=4, rx_filter=None):
         """Every setting of the reference's `sample_delay` knob (0 .. samples_per_bit - 1; rx.py:19): the

@@ -21,6 +21,10 @@
 //                       baseband by a converter at the same fcw with pa0 = -3 fcw, a 64-tap boxcar at decim 64, polar outputs:
 //                       one JSON line with the range of the magnitude (about am / 4) and of the phase (1/65536 turn: about 64 pm - 16384,
 //                       the tone being a sine and the converter's reference a cosine)
+//          carrier:     --carrier OFF [--fcw 1048576] [--am 16384] [--nco-samples 1e6]   carrier recovery (bbb_carrier_run): the NCO's
+//                       tone phase-modulated by half a turn per bit 1, 64 samples a bit, through a down-converter whose fcw lies
+//                       OFF (nonzero, |OFF| <= 4096) below the transmitter's.  Prints the errors the sign of Q leaves, those
+//                       left behind the recovery (L 32, init_phase 16384) and the estimated offset in turns per pair.
 //          sinc:        --sinc FILE [--eye-samples 1e6] [--prbs 31] [--nv 8] [--shape 16] [--shift 4]   the scope's 16x sinc
 //                       interpolator (bbb_sinc_*; gateware/bbb/sinc.py): one JSON line with the module's 1024 outputs for the
 //                       7-cycle sine of the reference's test, then the eye of a capture at 4 samples per bit (every second
@@ -226,7 +230,7 @@ int main(int argc, char **argv) {
     bool lags_set = false;
     int shape = 16, eye_shift = 4;
     double eye_samples = 1e6;
-    int tx_sweep = 0, nv_lo = 0, nv_hi = 15, fir = 0, dfe = 0, mlse = 0, timing = 0, fec = 0, rs = 0, rs_sigma = 42, sync_junk = -1, link = 0, link_delay = 2, errstat = 0, xcorr = 0, ddc = 0, nco_pm = 100;
+    int tx_sweep = 0, nv_lo = 0, nv_hi = 15, fir = 0, dfe = 0, mlse = 0, timing = 0, fec = 0, rs = 0, rs_sigma = 42, sync_junk = -1, link = 0, link_delay = 2, errstat = 0, xcorr = 0, ddc = 0, nco_pm = 100, carrier = 0;
     unsigned long errstat_guard = 64;
     unsigned long long init0 = 1;
     double bits = 1e9, from = 0, to = 10, step = 1, loopback = 0, nsamples = 0, grng_eval = 0;
@@ -285,6 +289,7 @@ int main(int argc, char **argv) {
         else if (a == "--errstat") errstat = std::atoi(v);
         else if (a == "--xcorr") xcorr = std::atoi(v);
         else if (a == "--ddc") ddc = std::atoi(v);
+        else if (a == "--carrier") carrier = std::atoi(v);
         else if (a == "--pm") nco_pm = std::atoi(v);
         else if (a == "--guard") errstat_guard = std::strtoul(v, nullptr, 0);
         else if (a == "--nv-range") {
@@ -385,6 +390,68 @@ int main(int argc, char **argv) {
         std::printf("{\"mode\": \"ddc\", \"samples\": %llu, \"outputs\": %llu, \"fcw\": %lu, \"am\": %lu, \"pm\": %d, \"mag_min\": %u, "
                     "\"mag_max\": %u, \"phase_min\": %d, \"phase_max\": %d, \"seconds\": %.6f}\n", (unsigned long long)n,
                     (unsigned long long)nout, nco_fcw, nco_am, nco_pm, mag_lo, mag_hi, ph_lo, ph_hi, dt);
+        return 0;
+    }
+
+    // ---- carrier recovery: the down-converter's tone with the two oscillators apart ------------------------------------------
+    if (carrier) {
+        if (nco_samples < 64 * 64 || nco_samples > 4e9 || nco_fcw >= (1ul << 24) || nco_fcw <= 4096 || nco_am >= (1ul << 16) || carrier < -4096 || carrier > 4096) {
+            std::fprintf(stderr, "--nco-samples 4096..4e9, 4096 < --fcw < 2^24, --am < 2^16, --carrier in [-4096, 4096]\n");
+            return 2;
+        }
+        const uint64_t nbits = (uint64_t)nco_samples / 64, n = nbits * 64;
+        std::vector<uint8_t> data(nbits);
+        std::vector<int16_t> pm(n);
+        uint64_t lcg = 5;
+        for (uint64_t b = 0; b < nbits; ++b) {
+            lcg = lcg * 6364136223846793005ull + 1442695040888963407ull;
+            data[b] = (uint8_t)(lcg >> 63);
+            for (int i = 0; i < 64; ++i) pm[b * 64 + i] = data[b] ? -512 : 0;
+        }
+        const bbb_nco_cfg cfg = {(uint32_t)nco_fcw, (uint32_t)nco_am, 0, 0};
+        const uint32_t rx_fcw = (uint32_t)((long)nco_fcw - carrier);
+        bbb_fir_cfg fc{};
+        fc.ntaps = 64;
+        for (int i = 0; i < 64; ++i) fc.taps[i] = 1;
+        fc.shift = 6, fc.decim = 64, fc.phase = 63;
+        const bbb_ddc_cfg dc = {rx_fcw, (uint32_t)((0x1000000ul - 3ul * rx_fcw % 0x1000000ul) & 0xFFFFFFul), BBB_DDC_IQ16};
+        const bbb_carrier_cfg cc = {32, 16384, 0, 0, 0};
+        const uint64_t npairs = nbits - 1, nwords = (npairs + 31) / 32 * 32 / 64 + 1;
+        bbb_nco *o = nullptr;
+        int16_t *x = nullptr, *pmd = nullptr, *iq = nullptr;
+        uint64_t *words = nullptr, *state = nullptr;                       // state[2] and stats[4] in one allocation
+        CHECK(bbb_nco_open(&cfg, 0, nullptr, &o));
+        if (hipMalloc((void **)&x, n * 2) != hipSuccess || hipMalloc((void **)&pmd, n * 2) != hipSuccess || hipMalloc((void **)&iq, npairs * 4) != hipSuccess ||
+            hipMalloc((void **)&words, nwords * 8) != hipSuccess || hipMalloc((void **)&state, 48) != hipSuccess ||
+            hipMemcpy(pmd, pm.data(), n * 2, hipMemcpyHostToDevice) != hipSuccess || hipMemset(state, 0, 48) != hipSuccess) {
+            std::fprintf(stderr, "hipMalloc failed\n");
+            return 1;
+        }
+        uint64_t nout = 0;
+        const double t0 = now_s();
+        CHECK(bbb_nco_run(o, nullptr, nullptr, pmd, n, x));
+        // the record is entered 3 samples late, the oscillator's latency, with those 3 as history: pair q is data bit q
+        CHECK(bbb_ddc_run(x + 3, n - 3, 3, 3, &dc, &fc, iq, &nout, 0, nullptr));
+        if (nout != npairs) { std::fprintf(stderr, "unexpected pair count\n"); return 1; }
+        CHECK(bbb_carrier_run(iq, npairs, 1, &cc, state, nullptr, words, nullptr, nullptr, state + 2, 0, nullptr));
+        if (hipDeviceSynchronize() != hipSuccess) { std::fprintf(stderr, "hipDeviceSynchronize failed\n"); return 1; }
+        const double dt = now_s() - t0;
+        std::vector<int16_t> hiq(2 * npairs);
+        std::vector<uint64_t> hw(nwords), hs(6);
+        if (hipMemcpy(hiq.data(), iq, npairs * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(hw.data(), words, nwords * 8, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(hs.data(), state, 48, hipMemcpyDeviceToHost) != hipSuccess) { std::fprintf(stderr, "copy failed\n"); return 1; }
+        (void)hipFree(x), (void)hipFree(pmd), (void)hipFree(iq), (void)hipFree(words), (void)hipFree(state);
+        CHECK(bbb_nco_close(o));
+        uint64_t before = 0, after = 0;
+        for (uint64_t q = 0; q < npairs; ++q) {
+            before += (hiq[2 * q + 1] > 0) != (data[q] != 0);
+            after += ((hw[q >> 6] >> (q & 63)) & 1) != data[q];
+        }
+        const double offset = hs[2] ? (double)(int64_t)hs[5] / ((double)hs[2] * 32.0 * 65536.0) : 0.0;
+        std::printf("{\"mode\": \"carrier\", \"samples\": %llu, \"bits\": %llu, \"fcw\": %lu, \"rx_fcw\": %u, \"errors_sign_of_q\": %llu, "
+                    "\"errors_recovered\": %llu, \"blocks\": %llu, \"offset_turns_per_pair\": %.9f, \"ideal_offset\": %.9f, \"seconds\": %.6f}\n",
+                    (unsigned long long)n, (unsigned long long)npairs, nco_fcw, rx_fcw, (unsigned long long)before, (unsigned long long)after,
+                    (unsigned long long)hs[2], offset, carrier * 64.0 / 16777216.0, dt);
         return 0;
     }
 

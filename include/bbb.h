@@ -884,6 +884,62 @@ int bbb_timing_run(const int16_t *in_dev, uint64_t nin, uint32_t nbefore, int fi
 int bbb_timing_model_host(const int16_t *in, uint64_t nin, uint32_t nbefore, int final, const bbb_timing_cfg *cfg, uint64_t *state,
                           uint64_t *bits_packed, void *soft, uint8_t *phase, uint64_t *stats, uint64_t *nbits_out);
 
+/* ---- carrier recovery: block phase estimate by squaring, unwrap, derotator, exact whatever the data are ------------------ */
+
+/* bbb_ddc_run's oscillator is a function of the sample number: nothing follows the transmitter's carrier.  With the two a few
+ * ppm apart the baseband vector of a BPSK signal turns slowly and neither I nor Q can be decided.  This block estimates the
+ * vector's angle block by block, unwraps it and turns every pair back, so that the data axis lands on I.  All integers, >>
+ * arithmetic, rom = bbb_nco_rom.
+ * in_dev: nin pairs (I, Q) of int16, the element BBB_DDC_IQ16 writes, 4-byte aligned.  L = block_pairs (a multiple of 8 in
+ * 8..1024; 0: 32).  Block j is the pairs [j L, (j + 1) L) below nin; nblocks = final ? ceil(nin / L) : floor(nin / L), so only
+ * the last block of a final call may be partial; a call that is not final ignores the pairs beyond nblocks * L.
+ *   block sums     SR_j = sum(I * I - Q * Q), SI_j = 2 * sum(I * Q) over the block's pairs: int64, at most 2^41 in magnitude
+ *                  (I * Q is summed and the sum doubled: 2 * I * Q of (-32768, -32768) does not fit int32)
+ *   doubled angle  m = max(|SR|, |SI|), s = max(0, bitlength(m) - 15); theta2_j = the phase of BBB_DDC_POLAR's CORDIC for the
+ *                  pair (SR >> s, SI >> s), both of which lie in [-32768, 32767]; (0, 0) gives 0
+ *                  h_j = (theta2_j mod 2^16) >> 1, in 0..32767: the carrier's phase modulo half a turn
+ *   unwrap         d = (h_j - est_(j-1)) mod 2^16; est_j = h_j if d < 16384 or d >= 49152, else (h_j + 32768) mod 2^16
+ *                  est_(-1) = init_phase (uint16, 1/65536 turn) for the first block after reset, else the state's
+ *   derotation     of every pair of block j: adr = est_j >> 6, c = rom[(adr + 256) mod 1024], s = rom[adr]
+ *                  I' = sat16((I * c + Q * s) >> 15)      Q' = sat16((Q * c - I * s) >> 15)
+ *                  (both sums stay below 46341 * 32767 < 2^31)
+ *   decision       bit = I' >= threshold (> with strict)
+ * Limits.  Squaring removes the data and with it half a turn: est is the carrier's phase or that plus half a turn.  Which one
+ * is fixed by init_phase (16384 makes bit 1 positive for a carrier phase-modulated as in the down-converter's example, -512
+ * for bit 1) or left to the frame synchroniser's polarity search.  The estimate is constant over a block, so the carrier may
+ * turn well below a quarter turn per block; a quarter turn or more per block breaks the unwrap.  BPSK only.
+ * chunk_blocks (0: the default) only places the boundaries of the device's work: no output depends on it. */
+typedef struct {
+    uint32_t block_pairs;      /* L: a multiple of 8 in 8..1024; 0: 32 */
+    uint32_t init_phase;       /* est_(-1) out of reset: 0..65535 in 1/65536 turn */
+    int32_t  threshold;
+    uint32_t strict;
+    uint32_t chunk_blocks;     /* blocks one workgroup scans; 0: the default */
+} bbb_carrier_cfg;
+
+/* The sizes of a call, from sizes alone (host only, works without a GPU; every output may be NULL): *nblocks as above,
+ * *nconsumed = min(nin, nblocks * L).  BBB_EINVAL for everything wrong with cfg, and for nin > 2^58. */
+int bbb_carrier_plan(const bbb_carrier_cfg *cfg, uint64_t nin, int final, uint64_t *nblocks, uint64_t *nconsumed);
+/* state_dev: uint64[2] on the device, read at the start and written at the end: [0] bit 63 is `started`, the low 16 bits are
+ * est of the last block; [1] the pairs consumed since reset (added to).  A zeroed state is out of reset.  A record cut at
+ * multiples of L and continued with these words, `final` on the last piece only, gives the outputs, stats and state of one
+ * call, bit for bit.  Outputs, each may be NULL, at least one must be given: iq_dev, nconsumed pairs (I', Q') (4-byte aligned;
+ * 16-byte aligned takes the wide stores); bits_packed_dev, LSB first in u64 words, all ceil(nblocks * L / 64) words are
+ * written, the bits from nconsumed on are 0; soft_dev, nconsumed int16, I'; phase_dev, uint16[nblocks], est_j.
+ * stats_dev (may be NULL): uint64[4], ADDED TO: blocks; blocks whose est changed sides, (est_j >> 15) != (est_(j-1) >> 15);
+ * blocks whose sums are both 0; the int64 sum of wrap16(est_j - est_(j-1)), which divided by blocks * L * 65536 is the carrier
+ * offset in turns per pair.  nin == 0 or nblocks == 0 only rewrites the state.  BBB_EINVAL before the device is touched:
+ * everything wrong with cfg, nulls, no output, nin > 2^58, misaligned pointers, outputs that overlap the pairs read or each
+ * other.  The call's scratch (4 bytes per block, 2 per chunk and 16 per workgroup of one pass) comes from the device's memory pool on hip_stream; there is
+ * no host round trip inside the call.  Asynchronous; a device without gfx950 gives BBB_ENODEV. */
+int bbb_carrier_run(const int16_t *in_dev, uint64_t nin, int final, const bbb_carrier_cfg *cfg, uint64_t *state_dev, int16_t *iq_dev,
+                    uint64_t *bits_packed_dev, int16_t *soft_dev, uint16_t *phase_dev, uint64_t *stats_dev, int device,
+                    void *hip_stream);
+/* The definition as a plain serial loop over host memory (works without a GPU): state[2], iq / bits_packed / soft / phase /
+ * stats as in bbb_carrier_run. */
+int bbb_carrier_model_host(const int16_t *in, uint64_t nin, int final, const bbb_carrier_cfg *cfg, uint64_t *state, int16_t *iq,
+                           uint64_t *bits_packed, int16_t *soft, uint16_t *phase, uint64_t *stats);
+
 /* ---- convolutional codec: encoder, puncturing, Viterbi decoder over soft or hard decisions, exact ---------------------- */
 
 /* Forward error correction for the receiver's decisions: a rate 1/n convolutional code of constraint length K, punctured or
