@@ -248,19 +248,21 @@ def test_slice_thresholds_and_word_boundaries(gpu):
 
 
 def test_indices_past_2_31(gpu):
-    """2^31 + 300 inputs filled on the device with x[i] = (7919 i mod 65536) - 32768: the outputs around index 2^31 - 1 and
-    the last ones against the model, on those slices only."""
+    """2^31 + 300 inputs filled on the device with x[i] = (7919 i mod 65521) - 32760: the outputs around index 2^31 - 1 and
+    the last ones against the model, on those slices only.  The fill's period matters: 65521 is prime, so x[i] differs from
+    x[i - 2^31] and from x[i - 2^32] at every i, and an input index that wrapped to a smaller one reads other data (with a
+    period of 65536, which divides both, it would read the same; tests/test_periodic_host.py holds both statements)."""
     n = (1 << 31) + 300
     x = torch.empty(n, dtype=torch.int16, device=DEV)
     step = 1 << 27
     for a in range(0, n, step):
         b = min(n, a + step)
-        x[a:b] = (((torch.arange(a, b, dtype=torch.int64, device=DEV) * 7919) & 0xFFFF) - 32768).to(torch.int16)
+        x[a:b] = (((torch.arange(a, b, dtype=torch.int64, device=DEV) * 7919) % 65521) - 32760).to(torch.int16)
 
     def pattern(a, b):
-        return (((np.arange(a, b, dtype=np.int64) * 7919) & 0xFFFF) - 32768).astype(np.int16)
+        return (((np.arange(a, b, dtype=np.int64) * 7919) % 65521) - 32760).astype(np.int16)
     h = [3000, -5000, 7000, -9000, 11000, -13000, 9000, -8535]
-    assert sum(abs(v) for v in h) == 65535
+    assert sum(abs(v) for v in h) == 65535 and 65535 * 32760 < 2 ** 31                 # |x| <= 32760: acc stays within int32
     f = bbb.FIR(h, shift=3)
     y = f.filter(x, out_dtype=torch.int32)
     assert y.numel() == n
