@@ -21,7 +21,7 @@ from .dfe import DFE, DFEStream                          # noqa: F401
 from .mlse import MLSE, MLSEStream                       # noqa: F401
 from .timing import TimingRecovery, TimingStream         # noqa: F401
 from .carrier import CarrierRecovery, CarrierStream      # noqa: F401
-from .fec import ConvCode, ConvStream, ReedSolomon, RSStream, Concatenated  # noqa: F401
+from .fec import ConvCode, ConvStream, ReedSolomon, RSStream, Concatenated, LDPC, LDPCStream  # noqa: F401
 from .framesync import FrameSync, FrameSyncStream        # noqa: F401
 from .link import LinkSweep                              # noqa: F401
 from .errstat import ErrorStats                          # noqa: F401

@@ -33,6 +33,7 @@ SYMBOLS = [
     "bbb_carrier_plan", "bbb_carrier_run", "bbb_carrier_model_host",
     "bbb_conv_plan", "bbb_conv_encode", "bbb_conv_encode_host", "bbb_conv_decode", "bbb_conv_model_host",
     "bbb_rs_encode", "bbb_rs_encode_host", "bbb_rs_decode", "bbb_rs_model_host",
+    "bbb_ldpc_encode", "bbb_ldpc_encode_host", "bbb_ldpc_decode", "bbb_ldpc_model_host",
     "bbb_framesync_plan", "bbb_framesync_run", "bbb_frame_extract", "bbb_frame_attach", "bbb_framesync_model_host",
     "bbb_frame_extract_host", "bbb_frame_attach_host",
 ]
@@ -164,6 +165,15 @@ class RSCfg(C.Structure):
     """bbb_rs_cfg"""
     _fields_ = [("prim_poly", C.c_uint32), ("fcr", C.c_uint32), ("prim", C.c_uint32), ("nroots", C.c_uint32), ("n", C.c_uint32),
                 ("depth", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+LDPC_NSTATS, LDPC_FAILED, LDPC_MAX_J, LDPC_MAX_K = 5, 255, 32, 64
+
+
+class LDPCCfg(C.Structure):
+    """bbb_ldpc_cfg"""
+    _fields_ = [("Z", C.c_uint32), ("J", C.c_uint32), ("K", C.c_uint32), ("max_iter", C.c_uint32), ("norm", C.c_uint32),
+                ("hard_mag", C.c_uint32), ("reserved", C.c_uint32 * 2), ("base", C.c_int16 * (LDPC_MAX_J * LDPC_MAX_K))]
 
 
 class DdcCfg(C.Structure):
@@ -347,6 +357,10 @@ def lib():
     l.bbb_rs_encode_host.argtypes = [vp, u64, C.POINTER(RSCfg), vp]
     l.bbb_rs_decode.argtypes = [vp, u64, C.POINTER(RSCfg), vp, vp, vp, i32, vp]
     l.bbb_rs_model_host.argtypes = [vp, u64, C.POINTER(RSCfg), vp, vp, vp]
+    l.bbb_ldpc_encode.argtypes = [vp, u64, C.POINTER(LDPCCfg), vp, i32, vp]
+    l.bbb_ldpc_encode_host.argtypes = [vp, u64, C.POINTER(LDPCCfg), vp]
+    l.bbb_ldpc_decode.argtypes = [vp, u64, u64, i32, C.POINTER(LDPCCfg), vp, vp, vp, i32, vp]
+    l.bbb_ldpc_model_host.argtypes = [vp, u64, u64, i32, C.POINTER(LDPCCfg), vp, vp, vp]
     fsc = C.POINTER(FrameSyncCfg)
     l.bbb_framesync_plan.argtypes = [u64, fsc, C.POINTER(FrameSyncPlan)]
     l.bbb_framesync_run.argtypes = [vp, u64, u64, i32, fsc, vp, vp, vp, u64, vp, i32, vp]

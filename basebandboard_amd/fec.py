@@ -307,6 +307,150 @@ class RSStream:
         return left
 
 
+class LDPC:
+    """Exact quasi-cyclic LDPC codec (include/bbb.h, bbb_ldpc_*): a layered normalised min-sum decoder over int16 posteriors and
+    an encoder for codes whose parity part is block upper triangular.  `base` is the J x K base matrix of Z x Z circulants
+    (-1: the zero block, s: the identity shifted by s); n = K Z coded bits, k = (K - J) Z data bits first, m = J Z checks.
+    `max_iter` 1..64 iterations of J layers; `norm` / 16 scales the check messages (1..16); a HARD bit counts as +-`hard_mag`.
+    A codeword whose checks are not all satisfied after max_iter iterations FAILED (iterations() gives 255) and its data bits
+    are the hard decisions as they stand.  No puncturing, no shortening, no soft outputs."""
+
+    def __init__(self, base, Z, max_iter=20, norm=12, hard_mag=32, device=0):
+        rows = [[int(v) for v in row] for row in base]
+        if not rows or not rows[0] or any(len(r) != len(rows[0]) for r in rows):
+            raise ValueError("base must be a J x K matrix")
+        self.base, self.Z, self.J, self.K = rows, int(Z), len(rows), len(rows[0])
+        self.max_iter, self.norm, self.hard_mag, self.device = int(max_iter), int(norm), int(hard_mag), int(device)
+        if self.J > _lib.LDPC_MAX_J:
+            raise ValueError("J must be 1..32")
+        if self.K > _lib.LDPC_MAX_K:
+            raise ValueError("K must be J + 1 .. 64")
+        if not 1 <= self.norm <= 16:
+            raise ValueError("norm must be 1..16")
+        if not 1 <= self.hard_mag <= 32767:
+            raise ValueError("hard_mag must be 1..32767")
+        if any(not -1 <= v < max(self.Z, 0) for r in rows for v in r):
+            raise ValueError("base entries must lie in -1 .. Z-1")
+        self._stats, self._iters = None, None
+        # everything else that is wrong with the code, from the library (host only)
+        _lib.check(_lib.lib().bbb_ldpc_model_host(None, 0, 0, _lib.CONV_SOFT16, C.byref(self._cfg()), None, None, None), "bbb_ldpc_model_host")
+
+    @classmethod
+    def array(cls, p, J, K, max_iter=20, norm=12, hard_mag=32, device=0):
+        """The triangular array code: p an odd prime, Z = p, J < K <= p; it needs no table and has an encoder."""
+        p, J, K = int(p), int(J), int(K)
+        if p < 3 or p % 2 == 0 or any(p % d == 0 for d in range(3, int(p ** 0.5) + 1, 2)):
+            raise ValueError("p must be an odd prime")
+        if not 1 <= J < K <= p:
+            raise ValueError("array codes need 1 <= J < K <= p")
+        base = [[j * (c + J - j) % p for c in range(K - J)] + [j * (i - j) % p if i >= j else -1 for i in range(J)] for j in range(J)]
+        return cls(base, p, max_iter, norm, hard_mag, device)
+
+    @property
+    def n(self):
+        return self.K * self.Z
+
+    @property
+    def k(self):
+        return (self.K - self.J) * self.Z
+
+    @property
+    def m(self):
+        return self.J * self.Z
+
+    @property
+    def rate(self):
+        """Data bits per coded bit, a Fraction."""
+        return Fraction(self.K - self.J, self.K)
+
+    def _cfg(self):
+        c = _lib.LDPCCfg()
+        c.Z, c.J, c.K, c.max_iter, c.norm, c.hard_mag = self.Z, self.J, self.K, self.max_iter, self.norm, self.hard_mag
+        for j, row in enumerate(self.base):
+            for i, v in enumerate(row):
+                c.base[j * self.K + i] = v
+        return c
+
+    def _stream_ptr(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def encode(self, bits, ncodewords):
+        """The coded bits of `ncodewords` blocks of k data bits packed contiguously in an int64 CUDA tensor (bbb_ldpc_encode):
+        (packed int64 tensor, ncodewords * n), codeword w's bit i at bit w n + i.  Asynchronous on the current torch stream."""
+        _lib.cuda_tensor("bits", bits, (torch.int64,), "int64", self.device)
+        ncodewords = int(ncodewords)
+        if not 0 <= ncodewords * self.k <= 64 * bits.numel():
+            raise ValueError("ncodewords * k bits must lie inside the tensor")
+        out = torch.empty((ncodewords * self.n + 63) // 64, dtype=torch.int64, device=bits.device)
+        _lib.check(_lib.lib().bbb_ldpc_encode(C.c_void_p(bits.data_ptr()), ncodewords, C.byref(self._cfg()), C.c_void_p(out.data_ptr()),
+                                              self.device, self._stream_ptr()), "bbb_ldpc_encode")
+        return out, ncodewords * self.n
+
+    def decode(self, values, hard=False, nbits=None):
+        """(packed int64 data bits, count) of the whole codewords among the received values (bbb_ldpc_decode); a ragged tail is
+        ignored.  hard=False: `values` is an int16 CUDA tensor of soft values (positive means 1, 0 an erasure).  hard=True: a
+        packed int64 CUDA tensor of `nbits` received bits, as RX.slice returns them.  iterations() then gives the byte per
+        codeword of this call.  Asynchronous on the current torch stream."""
+        if hard:
+            _lib.cuda_tensor("values", values, (torch.int64,), "int64", self.device)
+            if nbits is None or not 0 <= nbits <= 64 * values.numel():
+                raise ValueError("hard decisions need nbits, inside the tensor")
+            total = int(nbits)
+        else:
+            _lib.cuda_tensor("values", values, (torch.int16,), "int16", self.device)
+            total = values.numel()
+        ncw = total // self.n
+        bits = torch.empty((ncw * self.k + 63) // 64, dtype=torch.int64, device=values.device)
+        self._iters = torch.empty(ncw, dtype=torch.uint8, device=values.device)
+        if self._stats is None:
+            self._stats = torch.zeros(_lib.LDPC_NSTATS, dtype=torch.int64, device=values.device)
+        _lib.check(_lib.lib().bbb_ldpc_decode(C.c_void_p(values.data_ptr()), 0, ncw, _lib.CONV_HARD if hard else _lib.CONV_SOFT16,
+                                              C.byref(self._cfg()), C.c_void_p(bits.data_ptr()), C.c_void_p(self._iters.data_ptr()),
+                                              C.c_void_p(self._stats.data_ptr()), self.device, self._stream_ptr()), "bbb_ldpc_decode")
+        return bits, ncw * self.k
+
+    def iterations(self):
+        """The last decode call's byte per codeword (a uint8 CUDA tensor): 0 clean, 1..max_iter the iterations taken, 255 FAILED."""
+        if self._iters is None:
+            raise ValueError("no decode call yet")
+        return self._iters
+
+    def stream(self):
+        """An LDPCStream over int16 soft values: `push(chunk)` decodes the codewords that are complete so far, `finish()` says
+        how many values were left over."""
+        return LDPCStream(self)
+
+    def stats(self):
+        """What the decoder calls through this object added up (synchronises)."""
+        v = [0] * _lib.LDPC_NSTATS if self._stats is None else self._stats.cpu().tolist()
+        return dict(zip(("codewords", "clean", "failed", "iterations", "bits_corrected"), v))
+
+
+class LDPCStream:
+    """A received record decoded piece by piece: the values of an incomplete codeword are held back until the rest arrives, so
+    the pieces give the codewords of one call, each piece's data packed from its own bit 0.  Nothing lives on the device between
+    calls but those values."""
+
+    def __init__(self, code):
+        self.code, self.held = code, None
+
+    def push(self, chunk):
+        """(packed data bits, count, iterations) of the codewords this chunk completes (often none)."""
+        _lib.cuda_tensor("chunk", chunk, (torch.int16,), "int16", self.code.device)
+        b = chunk.reshape(-1)
+        buf = b if self.held is None or not self.held.numel() else torch.cat([self.held, b])
+        whole = buf.numel() // self.code.n * self.code.n
+        self.held = buf[whole:].clone()
+        bits, nbits = self.code.decode(buf[:whole].contiguous())
+        return bits, nbits, self.code.iterations()
+
+    def finish(self):
+        """The record ends here: the number of values of a last, incomplete codeword, which are dropped."""
+        left = 0 if self.held is None else self.held.numel()
+        self.held = None
+        return left
+
+
 class Concatenated:
     """The classic concatenation: an outer ReedSolomon around an inner ConvCode.  `decode` has the contract of
     ConvCode.decode for one final call from step 0, so RX.slice / count_errors / detect take it as `fec=`.  Without `sync`,

@@ -46,7 +46,8 @@ class RX:
         are decoded in one final call (bbb_conv_decode): the decoded bits and their count come back instead.  Soft decoding
         goes through ConvCode.decode on the int16 values of FIR.filter, DFE.equalize or TimingRecovery.recover.  fec may also
         be a fec.Concatenated (a ReedSolomon around a ConvCode): the Viterbi decoder's bytes are RS-decoded as well, and the
-        data bits of the whole frames come back."""
+        data bits of the whole frames come back.  Or a fec.LDPC: the decisions are the HARD received bits of its codewords from
+        bit 0 on (bbb_ldpc_decode), and the data bits of the whole codewords come back."""
         if fec is not None:
             bits, nbits = self.slice(samples, first_sample, stride, strict, rx_filter, dfe, mlse, timing)
             return fec.decode(bits, hard=True, nbits=nbits)

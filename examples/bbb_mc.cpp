@@ -55,6 +55,10 @@
 //                       (bbb_frame_attach), J >= 0 random bits put in front, the whole channel inverted; behind the Viterbi decoder
 //                       the frames are found and cut out (bbb_framesync_run, bbb_frame_extract; tol_search 2, tol_lock 6, verify 1,
 //                       flywheel 2) and handed to the RS decoder; the line gains the synchroniser's counters
+//          ldpc:        --ldpc P [--eye-samples 1e6] [--prbs 31] [--sigma 32]   the LDPC codec (bbb_ldpc_*): the whole codewords of the
+//                       array code array(P, 4, 16) (P an odd prime >= 17; 127: n = 2032, rate 3/4) that eye-samples PRBS bits fill,
+//                       encoded, sent as +-64 plus Gaussian noise of sigma made on the host, decoded from the soft values (max_iter 20,
+//                       norm 12): one JSON line with the channel's errors, the data errors behind the decoder and its statistics
 //          link:        --link 1 [--eye-samples 1e6] [--prbs 31] [--nv 8] [--shape 16] [--delay 2]   the bathtub of one transmitter
 //                       setting decided on the raw sample (bbb_tx_ber_sweep_*) and behind the moving average of rx.py:24-26
 //                       (bbb_link_sweep_* with the taps of bbb_fir_moving_average, the filtered stream re-timed by `delay`), the
@@ -230,7 +234,7 @@ int main(int argc, char **argv) {
     bool lags_set = false;
     int shape = 16, eye_shift = 4;
     double eye_samples = 1e6;
-    int tx_sweep = 0, nv_lo = 0, nv_hi = 15, fir = 0, dfe = 0, mlse = 0, timing = 0, fec = 0, rs = 0, rs_sigma = 42, sync_junk = -1, link = 0, link_delay = 2, errstat = 0, xcorr = 0, ddc = 0, nco_pm = 100, carrier = 0;
+    int tx_sweep = 0, nv_lo = 0, nv_hi = 15, fir = 0, dfe = 0, mlse = 0, timing = 0, fec = 0, rs = 0, rs_sigma = 42, ldpc = 0, ldpc_sigma = -1, sync_junk = -1, link = 0, link_delay = 2, errstat = 0, xcorr = 0, ddc = 0, nco_pm = 100, carrier = 0;
     unsigned long errstat_guard = 64;
     unsigned long long init0 = 1;
     double bits = 1e9, from = 0, to = 10, step = 1, loopback = 0, nsamples = 0, grng_eval = 0;
@@ -282,7 +286,8 @@ int main(int argc, char **argv) {
         else if (a == "--timing") timing = std::atoi(v);
         else if (a == "--fec") fec = std::atoi(v);
         else if (a == "--rs") rs = std::atoi(v);
-        else if (a == "--sigma") rs_sigma = std::atoi(v);
+        else if (a == "--ldpc") ldpc = std::atoi(v);
+        else if (a == "--sigma") rs_sigma = ldpc_sigma = std::atoi(v);
         else if (a == "--sync") sync_junk = std::atoi(v);
         else if (a == "--link") link = std::atoi(v);
         else if (a == "--delay") link_delay = std::atoi(v);
@@ -844,6 +849,60 @@ int main(int argc, char **argv) {
                     "\"seconds\": %.4f}\n", (unsigned long long)nbits, k, fec, cc.keep[0], cc.keep[1], 5 * nv, (unsigned long long)ntx,
                     (unsigned long long)e_channel, (unsigned long long)nd_hard, (unsigned long long)e_hard, (unsigned long long)nd_soft,
                     (unsigned long long)e_soft, secs);
+        return 0;
+    }
+
+    // ---- the LDPC codec: encode, noise, decode, counts (bbb_ldpc_*) ---------------------------------------------------------------------
+    if (ldpc) {
+        bool prime = ldpc >= 17 && ldpc <= 512 && (ldpc & 1);
+        for (int d = 3; prime && d * d <= ldpc; d += 2) prime = ldpc % d != 0;
+        if (ldpc_sigma == -1) ldpc_sigma = 32;
+        const uint32_t Z = (uint32_t)ldpc, J = 4, K = 16;
+        const uint64_t kbits = (uint64_t)(K - J) * Z, nbitsw = (uint64_t)K * Z, ncw = eye_samples < 1 || !prime ? 0 : (uint64_t)eye_samples / kbits;
+        if (!prime || ldpc_sigma < 0 || ldpc_sigma > 200 || ncw < 1) {
+            std::fprintf(stderr, "--ldpc P with P an odd prime 17..512, --sigma 0..200, --eye-samples at least one codeword of 12 P bits\n");
+            return 2;
+        }
+        bbb_ldpc_cfg lc{};
+        lc.Z = Z, lc.J = J, lc.K = K, lc.max_iter = 20, lc.norm = 12;
+        for (uint32_t j = 0; j < J; ++j) {
+            for (uint32_t c = 0; c < K - J; ++c) lc.base[j * K + c] = (int16_t)(j * (c + J - j) % Z);
+            for (uint32_t i = 0; i < J; ++i) lc.base[j * K + K - J + i] = (int16_t)(i >= j ? j * (i - j) % Z : -1);
+        }
+        const uint64_t ndata = ncw * kbits, ncoded = ncw * nbitsw;
+        uint64_t *data = nullptr, *coded = nullptr, *out = nullptr, *stats = nullptr, e_data = 0, e_channel = 0;
+        int16_t *soft = nullptr;
+        if (hipMalloc((void **)&data, (ndata / 64 + 1) * 8) != hipSuccess || hipMalloc((void **)&coded, (ncoded / 64 + 1) * 8) != hipSuccess ||
+            hipMalloc((void **)&out, (ndata / 64 + 1) * 8) != hipSuccess || hipMalloc((void **)&stats, BBB_LDPC_NSTATS * 8) != hipSuccess ||
+            hipMalloc((void **)&soft, ncoded * sizeof(int16_t)) != hipSuccess || hipMemset(stats, 0, BBB_LDPC_NSTATS * 8) != hipSuccess) {
+            std::fprintf(stderr, "hipMalloc failed\n");
+            return 1;
+        }
+        CHECK(bbb_prbs_fill(k, 1, 0, ndata, data, 0, nullptr));
+        const double t0 = now_s();
+        CHECK(bbb_ldpc_encode(data, ncw, &lc, coded, 0, nullptr));
+        std::vector<uint64_t> txh((size_t)(ncoded + 63) / 64);
+        if (hipMemcpy(txh.data(), coded, txh.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) { std::fprintf(stderr, "copy failed\n"); return 1; }
+        std::vector<int16_t> x((size_t)ncoded);
+        std::mt19937_64 gen(44);
+        std::normal_distribution<double> noise(0.0, (double)ldpc_sigma);
+        for (uint64_t i = 0; i < ncoded; ++i) {
+            const bool b = txh[(size_t)(i >> 6)] >> (i & 63) & 1;
+            x[(size_t)i] = (int16_t)((b ? 64 : -64) + std::lrint(noise(gen)));
+            e_channel += (uint64_t)((x[(size_t)i] > 0) != b);
+        }
+        if (hipMemcpy(soft, x.data(), ncoded * sizeof(int16_t), hipMemcpyHostToDevice) != hipSuccess) { std::fprintf(stderr, "copy failed\n"); return 1; }
+        CHECK(bbb_ldpc_decode(soft, 0, ncw, BBB_CONV_SOFT16, &lc, out, nullptr, stats, 0, nullptr));
+        CHECK(bbb_prbs_check(k, 1, 0, ndata, out, &e_data, 0, nullptr));
+        uint64_t st[BBB_LDPC_NSTATS];
+        if (hipMemcpy(st, stats, sizeof st, hipMemcpyDeviceToHost) != hipSuccess) { std::fprintf(stderr, "copy failed\n"); return 1; }
+        const double secs = now_s() - t0;
+        for (void *p : {(void *)data, (void *)coded, (void *)out, (void *)stats, (void *)soft}) (void)hipFree(p);
+        std::printf("{\"mode\": \"ldpc\", \"code\": \"array(%d,4,16)\", \"n\": %llu, \"k\": %llu, \"codewords\": %llu, \"data_bits\": %llu, \"prbs\": %d, "
+                    "\"sigma\": %d, \"coded_bits\": %llu, \"channel_errors\": %llu, \"data_errors\": %llu, \"clean\": %llu, \"failed\": %llu, "
+                    "\"iterations\": %llu, \"bits_corrected\": %llu, \"seconds\": %.4f}\n", ldpc, (unsigned long long)nbitsw, (unsigned long long)kbits,
+                    (unsigned long long)st[0], (unsigned long long)ndata, k, ldpc_sigma, (unsigned long long)ncoded, (unsigned long long)e_channel,
+                    (unsigned long long)e_data, (unsigned long long)st[1], (unsigned long long)st[2], (unsigned long long)st[3], (unsigned long long)st[4], secs);
         return 0;
     }
 

@@ -1192,6 +1192,70 @@ int bbb_rs_decode(const uint8_t *in_dev, uint64_t nframes, const bbb_rs_cfg *cfg
 int bbb_rs_model_host(const uint8_t *in, uint64_t nframes, const bbb_rs_cfg *cfg, uint8_t *data, uint8_t *nerr /* may be NULL */,
                       uint64_t *stats /* may be NULL */);
 
+/* ---- LDPC codec: quasi-cyclic codes, layered normalised min-sum decoder, triangular encoder ---- */
+
+/* An iteratively decoded block code for the receiver's soft or hard decisions.  All integers.
+ * Code:  a base matrix base[j][c], j < J block rows, c < K block columns of Z x Z circulants (row-major J x K in cfg->base).
+ *        Entry -1 is the zero block, entry s in 0..Z-1 the identity shifted by s: check j Z + r involves variable
+ *        c Z + (r + s) mod Z.  n = K Z coded bits, m = J Z checks, k = (K - J) Z data bits; systematic, data first.
+ *        Bounds (part of the ABI): Z 2..512, J 1..32, J < K <= 64, n <= 16384, m <= 8192, every block row holds 2..32 entries
+ *        >= 0, every block column at least one, entries lie in -1..Z-1.  Cycles are not checked.
+ * Decoder: received values as bbb_conv_decode's: BBB_CONV_SOFT16 (int16, positive means 1, 0 an erasure) or BBB_CONV_HARD
+ *        (packed bits, a bit counts as +hard_mag / -hard_mag).  Per codeword, with r[v] its n values:
+ *          P[v] = clamp(r[v], +-32767), R[c][e] = 0 for every check c and every edge e of it; hard(v) = P[v] > 0.
+ *          If every check of hard is satisfied the codeword is done with iters = 0.  Otherwise for it = 0 .. max_iter - 1:
+ *            for j = 0 .. J - 1 in this order, for every row r < Z of layer j (check c = j Z + r; its edges e run over the
+ *            entries >= 0 of block row j by ascending column, v_e the variable of edge e):
+ *              Q_e = clamp(P[v_e] - R[c][e], +-32767), b_e = Q_e > 0, S = XOR of the b_e
+ *              i1 = the lowest e with the smallest |Q_e|, m1 that value, m2 the smallest |Q_e| over e != i1
+ *              a_e = ((e == i1 ? m2 : m1) * norm) >> 4
+ *              R[c][e] = (S ^ b_e) ? +a_e : -a_e,  P[v_e] = clamp(Q_e + R[c][e], +-32767)
+ *            after layer J - 1: if every check of hard is satisfied, stop with iters = it + 1.
+ *          After max_iter iterations without that the codeword has FAILED: iters = 255 (BBB_LDPC_FAILED).
+ *          The output is hard(v) for v < k of the final P in every case.
+ *        A block column has at most one circulant in a block row, so the checks of a layer touch disjoint variables: their order
+ *        within the layer does not matter, and the device runs them at once.  Storing R as (m1 norm >> 4, m2 norm >> 4, i1 and
+ *        the bits S ^ b_e) is equivalent, and is what the device keeps.  max_iter 1..64; norm 1..16, 0 means 12; hard_mag
+ *        1..32767, 0 means 32.  |Q_e + R| < 2^17: int32 is exact throughout.
+ * Encoder: for codes whose parity part is block upper triangular: base[j][K-J+i] = -1 for i < j and >= 0 for i = j.  x[0..k)
+ *        is the data; for j = J - 1 down to 0, for r < Z: t_r = the XOR, over the entries of row j other than (j, K-J+j), of
+ *        x[c Z + (r + s) mod Z]; then x[(K-J+j) Z + (r + s_jj) mod Z] = t_r.  Other base matrices decode but do not encode
+ *        (BBB_EINVAL, "parity part not triangular").  The triangular array code array(p, J, K) needs no table: p an odd prime,
+ *        Z = p, J < K <= p, base[j][c] = j (c + J - j) mod p for c < K - J, parity column i: j (i - j) mod p for i >= j, else -1.
+ * Layouts: codeword w's values are elements in_first + w n ... of in_dev (bits for HARD), in_dev the BASE of the buffer,
+ *        2-byte aligned for SOFT16 and 8-byte aligned for HARD.  Decoded data are packed contiguously: codeword w's bit i is bit
+ *        w k + i of bits_packed_dev (8-byte aligned, LSB first in u64 words), the unused bits of the last word 0, words beyond it
+ *        untouched; nothing depends on the buffer's old contents.  The encoder reads data in that layout and writes codeword
+ *        w's bit i to bit w n + i of out_dev, packed the same way.
+ * Outputs: iters_dev (may be NULL): one byte per codeword.  stats_dev (may be NULL, 8-byte aligned): uint64[BBB_LDPC_NSTATS],
+ *        ADDED TO: codewords, clean (iters 0), failed, iterations summed over the converged codewords, bits corrected (the
+ *        popcount over all n bits of (clamped r > 0) ^ hard, over the converged codewords).
+ * Codewords are independent and there is no device state: any cutting of a record at codeword boundaries gives the outputs
+ * of one call.  ncodewords = 0 writes nothing.  The device calls are asynchronous on hip_stream.  BBB_EINVAL (with a detail,
+ * before the device is touched): every bound above, reserved != 0, an unknown format, null or misaligned pointers, any two
+ * buffers that overlap, ncodewords n > 2^40, in_first > 2^62.  A device without gfx950 gives BBB_ENODEV.
+ * Out of scope: puncturing, shortening, dual-diagonal and accumulator encoders, soft outputs, flooding schedules. */
+#define BBB_LDPC_NSTATS 5
+#define BBB_LDPC_FAILED 255
+#define BBB_LDPC_MAX_J 32
+#define BBB_LDPC_MAX_K 64
+typedef struct {
+    uint32_t Z, J, K;
+    uint32_t max_iter, norm, hard_mag;
+    uint32_t reserved[2];
+    int16_t  base[BBB_LDPC_MAX_J * BBB_LDPC_MAX_K];   /* row-major J x K: base[j * K + c]; entries beyond J K are ignored */
+} bbb_ldpc_cfg;
+int bbb_ldpc_decode(const void *in_dev, uint64_t in_first, uint64_t ncodewords, int format, const bbb_ldpc_cfg *cfg,
+                    uint64_t *bits_packed_dev, uint8_t *iters_dev /* may be NULL */, uint64_t *stats_dev /* may be NULL */, int device,
+                    void *hip_stream);
+int bbb_ldpc_encode(const uint64_t *bits_dev, uint64_t ncodewords, const bbb_ldpc_cfg *cfg, uint64_t *out_dev, int device,
+                    void *hip_stream);
+/* The decoder's definition as a plain serial loop over host memory with R kept per edge; works without a GPU. */
+int bbb_ldpc_model_host(const void *in, uint64_t in_first, uint64_t ncodewords, int format, const bbb_ldpc_cfg *cfg,
+                        uint64_t *bits_packed, uint8_t *iters /* may be NULL */, uint64_t *stats /* may be NULL */);
+/* The encoder as a serial loop over host memory; works without a GPU. */
+int bbb_ldpc_encode_host(const uint64_t *bits, uint64_t ncodewords, const bbb_ldpc_cfg *cfg, uint64_t *out);
+
 /* ---- Frame synchroniser: marker search, lock, derandomiser ------------------------------------ */
 
 /* Finds the frames of a packed bit stream that starts anywhere: in front of bbb_rs_decode, behind bbb_conv_decode.
